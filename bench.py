@@ -7,8 +7,14 @@ en_US-lessac-medium at 1/2/4/8 MI355X — data-parallel utterance batching,
 one rank per GPU over RCCL, weak scaling (fixed per-GPU batch).
 
 Usage (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   # N>1 is launched via torch.distributed.run, one rank per GPU.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time K steps, print one JSON line.  --dump-outputs DIR also writes what
+the last timed step returned (audio, audio_lengths) as float32 .npy
+files, so two builds can be compared output for output.  --full is the
+switch for every measurement beyond the headline figure (none today).
 
 A "step" = one full synthesis of a fixed batch of synthetic phoneme
 sequences (text encoder + duration predictor + flow + HiFi-GAN decode)
@@ -47,6 +53,35 @@ def make_batch(batch: int, seq_len: int, n_vocab: int, device, seed: int):
     return ids.to(device), lengths.to(device)
 
 
+DUMP_BUDGET_BYTES = 60 * 10**6  # whole job: a dump stays under 64 MB
+
+
+def dump_outputs(out_dir: str, outputs: dict, rank: int, world: int):
+    """Write each output tensor of the last timed step as float32
+    `<name>.npy` (rank 0) / `<name>.rank<r>.npy` (other ranks).  An output
+    larger than its share of the budget is reduced to a fixed, seeded
+    sample of its flattened elements, so the same shape always yields the
+    same sample positions."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: t.detach().to("cpu", torch.float32).contiguous().numpy()
+              for name, t in outputs.items()}
+    remaining = DUMP_BUDGET_BYTES // max(world, 1)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    # smallest first, so what the small outputs leave goes to the large ones
+    order = sorted(arrays, key=lambda n: arrays[n].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = remaining // (len(order) - i)
+        if a.nbytes > share:
+            rng = np.random.default_rng(20240229)
+            idx = np.sort(rng.integers(0, a.size, size=share // 4))
+            a = a.reshape(-1)[idx]
+        remaining -= a.nbytes
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -63,7 +98,15 @@ def main():
     ap.add_argument("--engine", choices=["cpp", "python"], default="cpp",
                     help="serving runtime: the C++ VitsEngine (default) or "
                          "the Python model path (same kernels either way)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (there is none today: the run is the same)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -121,11 +164,14 @@ def main():
 
             ext = hip_ext(required=False)
             if ext is not None and hasattr(ext, "VitsEngine"):
-                tmp = tempfile.mkdtemp(prefix=f"bench_voice_r{rank}_")
-                pack = create_random_voice(
-                    tmp, "bench", quality=args.quality, seed=0)
-                engine = ext.VitsEngine(
-                    pack, str(device), "bf16" if use_gpu else "f32")
+                # the engine reads the whole pack at construction, so the
+                # directory can go as soon as it exists
+                with tempfile.TemporaryDirectory(
+                        prefix=f"bench_voice_r{rank}_") as tmp:
+                    pack = create_random_voice(
+                        tmp, "bench", quality=args.quality, seed=0)
+                    engine = ext.VitsEngine(
+                        pack, str(device), "bf16" if use_gpu else "f32")
         except Exception as e:  # noqa: BLE001 - fall back to python path
             print(f"# engine=cpp unavailable ({e}); using python path",
                   flush=True)
@@ -137,13 +183,17 @@ def main():
 
     seeds = [1234 * (rank + 1) + i for i in range(args.batch)]
 
+    last = {}  # what the most recent step returned (for --dump-outputs)
+
     def one_step():
+        last.clear()  # release the previous step's outputs first, as before
         if engine is not None:
             audio, audio_lengths = engine.infer(
                 ids, lengths, None, 0.667, 1.0, 0.8, seeds)
         else:
             with torch.no_grad():
                 audio, audio_lengths = net.infer(ids, lengths)
+        last["audio"], last["audio_lengths"] = audio, audio_lengths
         return float(audio_lengths.sum().item()) / sample_rate
 
     # ---- warmup --------------------------------------------------------- #
@@ -165,6 +215,9 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
 
     # max elapsed over ranks; sum audio over ranks
     if dist:
