@@ -29,17 +29,23 @@ __global__ void layer_norm_ct_kernel(const T* __restrict__ x,
   const long base = (b * C) * T_len + t;
   const T* xp = x + base;
   const T* rp = HAS_RES ? res + base : nullptr;
-  // single pass: sum + sum of squares (C is small, f32 accumulate)
-  float s = 0.f, ss = 0.f;
+  // two passes (mean, then centred sum of squares): ss/C - mean^2 in one
+  // f32 pass cancels catastrophically when |mean| >> std
+  float s = 0.f;
   for (int c = 0; c < C; ++c) {
     float v = ld_f(xp + (long)c * T_len);
     if (HAS_RES) v += ld_f(rp + (long)c * T_len);
     s += v;
-    ss += v * v;
   }
   const float mean = s / C;
-  const float var = ss / C - mean * mean;
-  const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+  float ss = 0.f;
+  for (int c = 0; c < C; ++c) {
+    float v = ld_f(xp + (long)c * T_len);
+    if (HAS_RES) v += ld_f(rp + (long)c * T_len);
+    v -= mean;
+    ss += v * v;
+  }
+  const float rstd = rsqrtf(ss / C + eps);
   T* op = out + base;
   for (int c = 0; c < C; ++c) {
     float v = ld_f(xp + (long)c * T_len);
@@ -77,25 +83,33 @@ __global__ void layer_norm_ct_split_kernel(const T* __restrict__ x,
   const int cq = (C + SPLIT - 1) / SPLIT;
   const int c_lo = part * cq;
   const int c_hi = min(c_lo + cq, C);
-  float s = 0.f, ss = 0.f;
+  float s = 0.f;
   if (live) {
     for (int c = c_lo; c < c_hi; ++c) {
       float v = ld_f(xp + (long)c * T_len);
       if (HAS_RES) v += ld_f(rp + (long)c * T_len);
       s += v;
-      ss += v * v;
     }
   }
   // combine the SPLIT part-lanes of each token (they sit TOK apart)
 #pragma unroll
-  for (int d = TOK; d < 64; d <<= 1) {
-    s += __shfl_xor(s, d, 64);
-    ss += __shfl_xor(ss, d, 64);
-  }
-  if (!live) return;
+  for (int d = TOK; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
   const float mean = s / C;
-  const float var = ss / C - mean * mean;
-  const float rstd = rsqrtf(fmaxf(var, 0.f) + eps);
+  // second pass + second butterfly: centred sum of squares (stable under
+  // a channel offset, unlike ss/C - mean^2)
+  float ss = 0.f;
+  if (live) {
+    for (int c = c_lo; c < c_hi; ++c) {
+      float v = ld_f(xp + (long)c * T_len);
+      if (HAS_RES) v += ld_f(rp + (long)c * T_len);
+      v -= mean;
+      ss += v * v;
+    }
+  }
+#pragma unroll
+  for (int d = TOK; d < 64; d <<= 1) ss += __shfl_xor(ss, d, 64);
+  if (!live) return;
+  const float rstd = rsqrtf(ss / C + eps);
   T* op = out + base;
   for (int c = c_lo; c < c_hi; ++c) {
     float v = ld_f(xp + (long)c * T_len);

@@ -387,14 +387,24 @@ def resblock_pair_cl(
     """Fused resblock conv pair: (conv2_{k,1}(lrelu(conv1_{k,d}(lrelu(x))))
     + x [+ accum]) * out_scale, channel-last, intermediate tensor kept in
     LDS (csrc/resblock_cl.hip).  `accum`/`out_scale` fold the MRF
-    cross-resblock sum and /num_kernels into the epilogue."""
+    cross-resblock sum and /num_kernels into the epilogue.  Shapes the
+    fused kernel does not take (halo (k-1)*dilation > 52, channel counts
+    that do not pad to a square 32/64/128/256 weight) run as two convs."""
     Cout, Cin, k = w1.shape
-    if (use_hip(x) and Cin == Cout and b1 is not None and b2 is not None
-            and (k - 1) * dilation <= 64):
+    fused = (use_hip(x) and Cin == Cout and w2.shape == w1.shape
+             and b1 is not None and b2 is not None
+             and (k - 1) * dilation <= 52)
+    if fused:
+        # the kernel is instantiated for square padded weights of 32, 64,
+        # 128 or 256 channels only (e.g. C=96 pads to 128x96: not square)
+        w1p, w2p = _conv_weight_mfma(w1), _conv_weight_mfma(w2)
+        fused = (w1p.shape[1] == w1p.shape[2] and w2p.shape == w1p.shape
+                 and w1p.shape[1] in (32, 64, 128, 256))
+    if fused:
         ext = hip_ext(required=True)
         return ext.resblock_pair_cl_fused(
-            x.contiguous(), _conv_weight_mfma(w1), _bias_f32(b1),
-            _conv_weight_mfma(w2), _bias_f32(b2), k, dilation,
+            x.contiguous(), w1p, _bias_f32(b1), w2p, _bias_f32(b2),
+            k, dilation,
             _lens_i32(out_lens, x.device),
             accum.contiguous() if accum is not None else None,
             float(out_scale),
