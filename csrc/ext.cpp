@@ -79,6 +79,18 @@ torch::Tensor resblock_chain_cl_fused(
     torch::Tensor x, torch::Tensor w_all, torch::Tensor b_all, long k,
     long d1, long d2, long d3, c10::optional<torch::Tensor> out_lens,
     c10::optional<torch::Tensor> accum, double out_scale);
+// prosody.hip
+torch::Tensor resample_linear_rows(torch::Tensor x, torch::Tensor in_len,
+                                   torch::Tensor out_len, long N_out_max);
+torch::Tensor scale_rows(torch::Tensor x, torch::Tensor len,
+                         torch::Tensor gain);
+std::vector<torch::Tensor> wsola_rows(torch::Tensor x, torch::Tensor in_len,
+                                      torch::Tensor ana_hop,
+                                      torch::Tensor n_frames,
+                                      torch::Tensor out_len,
+                                      torch::Tensor window, long half,
+                                      long search, torch::Tensor gain,
+                                      long N_out_max, long K_max);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "sonata_amd hand-written CDNA4 (gfx950) kernels";
@@ -117,6 +129,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused relative-position attention (QKT+band+softmax+PV+rel_v)",
         py::arg("qkv"), py::arg("rel_k"), py::arg("rel_v"), py::arg("lens"),
         py::arg("heads"), py::arg("window"), py::arg("scale"));
+  m.def("resample_linear_rows", &resample_linear_rows,
+        "per-row linear resampling of [B,N] f32, positions in double");
+  m.def("scale_rows", &scale_rows, "per-row gain of [B,N] f32");
+  m.def("wsola_rows", &wsola_rows,
+        "per-row WSOLA time stretch; returns (y, targets)",
+        py::arg("x"), py::arg("in_len"), py::arg("ana_hop"),
+        py::arg("n_frames"), py::arg("out_len"), py::arg("window"),
+        py::arg("half"), py::arg("search"), py::arg("gain"),
+        py::arg("n_out_max"), py::arg("k_max"));
 
   // C++ inference runtime (csrc/engine): the ort-replacement executor.
   py::class_<sonata::VitsEngine>(m, "VitsEngine")

@@ -24,6 +24,7 @@ ext = CUDAExtension(
         "csrc/conv1d_cl.hip",
         "csrc/resblock_cl.hip",
         "csrc/attention_cl.hip",
+        "csrc/prosody.hip",
         "csrc/engine/vits_engine.cpp",
     ],
     extra_compile_args={

@@ -101,3 +101,40 @@ def apply_prosody(
     if abs(volume - 1.0) >= 1e-6:
         y = y * np.float32(volume)
     return y
+
+
+# --------------------------------------------------------------------------- #
+# shared length / position arithmetic (used by the batched ops on both
+# backends: the HIP kernels take every length from here and never re-derive
+# one).  Same expressions, same Python float (double) arithmetic as
+# time_stretch_wsola / resample_linear above.
+# --------------------------------------------------------------------------- #
+def wsola_plan(
+    n: int,
+    speed: float,
+    sample_rate: int,
+    frame_ms: float = 30.0,
+    search_ms: float = 10.0,
+):
+    """(frame, half, search, ana_hop, n_frames, n_out) of time_stretch_wsola
+    for an n-sample row."""
+    frame = max(int(sample_rate * frame_ms / 1000.0), 64)
+    half = frame // 2
+    frame = half * 2
+    search = max(int(sample_rate * search_ms / 1000.0), 16)
+    ana_hop = half * speed
+    n_frames = max(int((n - frame - search) / ana_hop), 1)
+    n_out = min(n_frames * half + frame, int(n / speed))
+    return frame, half, search, ana_hop, n_frames, n_out
+
+
+def resample_out_len(n: int, ratio: float) -> int:
+    """Output length of resample_linear for an n-sample row."""
+    return max(int(round(n / ratio)), 1)
+
+
+def wsola_is_passthrough(n: int, speed: float, frame: int) -> bool:
+    """Rows the batched entry points copy unchanged: speed ~ 1 (as
+    time_stretch_wsola does), empty rows, and rows shorter than one frame
+    (where the single-row function has no defined behaviour)."""
+    return n == 0 or abs(speed - 1.0) < 1e-3 or n < frame

@@ -207,11 +207,15 @@ class SonataGrpcService:
         # default (parallel/batched): sentences go through the dynamic
         # batcher so CONCURRENT RPCs share padded GPU batches
         sentences = list(v.synth.model.phonemize_text(request.text))
-        futures = [v.batcher.submit(sent) for sent in sentences]
+        # prosody rides with the request into the coalesced batch when
+        # the device path is on; _post then only appends silence
+        on_device = v.synth.device_prosody(out_cfg)
+        triple = out_cfg.prosody_triple() if on_device else None
+        futures = [v.batcher.submit(sent, triple) for sent in sentences]
         for f in futures:
             audio = f.result()
             if out_cfg is not None:
-                audio = v.synth._post(audio, out_cfg)
+                audio = v.synth._post(audio, out_cfg, prosody_done=on_device)
             yield MESSAGES["SynthesisResult"](
                 wav_samples=audio.as_wave_bytes(),
                 rtf=float(audio.real_time_factor),

@@ -139,10 +139,33 @@ class VitsVoice(SonataModel):
     def speak_one_sentence(self, phonemes: str) -> Audio:
         return self.speak_batch([phonemes])[0]
 
+    @property
+    def supports_device_prosody(self) -> bool:
+        """speak_batch(prosody=...) applies rate / volume / pitch to the
+        batch on the model's device, before the copy to the host."""
+        return True
+
+    def _prosody_rows(self, audio, audio_lengths, prosody):
+        """Per-row (speed, volume, pitch) on the [B, 1, T] decoder output;
+        rows given as None are left as they are."""
+        from ..ops import apply_prosody_rows
+
+        rows = [p if p is not None else (1.0, 1.0, 1.0) for p in prosody]
+        assert len(rows) == audio.shape[0], "one prosody triple per row"
+        y, out_lengths = apply_prosody_rows(
+            audio.float()[:, 0, :], audio_lengths, self.config.sample_rate,
+            speed=[r[0] for r in rows], volume=[r[1] for r in rows],
+            pitch=[r[2] for r in rows])
+        return y.unsqueeze(1), out_lengths
+
     @torch.no_grad()
-    def speak_batch(self, phonemes_batch: Sequence[str]) -> List[Audio]:
+    def speak_batch(self, phonemes_batch: Sequence[str],
+                    prosody=None) -> List[Audio]:
         """True padded [B, T] batching (the reference loops batch=1:
-        piper/src/lib.rs:425-437 — batching is a headline improvement)."""
+        piper/src/lib.rs:425-437 — batching is a headline improvement).
+
+        `prosody`: optional per-row sequence of (speed, volume, pitch) or
+        None; applied on the device tensor before the single host copy."""
         cfg = self.get_synthesis_config()
         id_lists = [self._encode_ids(p) for p in phonemes_batch]
         B = len(id_lists)
@@ -170,6 +193,9 @@ class VitsVoice(SonataModel):
             infer_ms = (time.perf_counter() - t0) * 1000.0
             info = self.audio_output_info()
             out: List[Audio] = []
+            if prosody is not None:
+                audio, audio_lengths = self._prosody_rows(
+                    audio, audio_lengths, prosody)
             audio = audio.float().cpu().numpy()
             audio_lengths = audio_lengths.cpu().numpy()
             for b in range(B):
@@ -193,6 +219,9 @@ class VitsVoice(SonataModel):
 
         info = self.audio_output_info()
         out: List[Audio] = []
+        if prosody is not None:
+            audio, audio_lengths = self._prosody_rows(
+                audio, audio_lengths, prosody)
         audio = audio.float().cpu().numpy()
         audio_lengths = audio_lengths.cpu().numpy()
         for b in range(B):

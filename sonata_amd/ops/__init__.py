@@ -71,4 +71,7 @@ from .functional import (  # noqa: F401,E402
     depthwise_conv1d_cl,
     attn_relpos_cl,
     row_ln_cl,
+    resample_linear_rows,
+    wsola_rows,
+    apply_prosody_rows,
 )

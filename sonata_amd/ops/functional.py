@@ -568,3 +568,199 @@ def row_ln_cl(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
     if residual is not None:
         x = x + residual
     return F.layer_norm(x, (x.shape[-1],), gamma, beta, eps)
+
+
+# --------------------------------------------------------------------------- #
+# batched prosody: rate / pitch / volume on [B, N] f32 rows with per-row
+# parameters (csrc/prosody.hip).  The CPU path calls the NumPy functions of
+# audio.prosody row by row and is the oracle; every length on both paths
+# comes from audio.prosody.wsola_plan / resample_out_len.
+# --------------------------------------------------------------------------- #
+def _row_lengths(lengths, B: int):
+    """Per-row lengths as Python ints (host arithmetic decides every
+    output length)."""
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.detach().cpu().tolist()
+    out = [int(v) for v in lengths]
+    assert len(out) == B, "one length per row"
+    return out
+
+
+def _per_row(v, B: int, default: float = 1.0):
+    if v is None:
+        return [default] * B
+    if isinstance(v, (int, float)):
+        return [float(v)] * B
+    out = [float(t) for t in v]
+    assert len(out) == B, "one parameter per row"
+    return out
+
+
+def _rows_from_numpy(rows, device) -> tuple:
+    """List of 1-D f32 arrays -> zero-padded [B, max_len] tensor + lengths."""
+    import numpy as np
+
+    lens = [int(r.shape[0]) for r in rows]
+    y = np.zeros((len(rows), max(lens, default=0)), dtype=np.float32)
+    for b, r in enumerate(rows):
+        y[b, : lens[b]] = r
+    return (torch.from_numpy(y).to(device),
+            torch.tensor(lens, dtype=torch.long))
+
+
+def _i32(vals, device) -> torch.Tensor:
+    return torch.tensor(vals, dtype=torch.int32, device=device)
+
+
+def resample_linear_rows(x: torch.Tensor, lengths, ratio):
+    """Per-row linear resampling of x [B, N] f32 by `ratio[b]` (output
+    length = lengths[b]/ratio[b]); rows with |ratio-1| < 1e-6 and empty
+    rows are copied.  Returns (y [B, max out_len] zero-padded, out_lengths)."""
+    from ..audio import prosody as P
+
+    B = x.shape[0]
+    lens = _row_lengths(lengths, B)
+    ratios = _per_row(ratio, B)
+    if not use_hip(x):
+        xn = x.detach().cpu().numpy()
+        return _rows_from_numpy(
+            [P.resample_linear(xn[b, : lens[b]], ratios[b])
+             for b in range(B)], x.device)
+    ext = hip_ext(required=True)
+    out = [n if (n == 0 or abs(r - 1.0) < 1e-6) else P.resample_out_len(n, r)
+           for n, r in zip(lens, ratios)]
+    y = ext.resample_linear_rows(
+        x.contiguous(), _i32(lens, x.device), _i32(out, x.device),
+        max(out, default=0))
+    return y, torch.tensor(out, dtype=torch.long)
+
+
+def _wsola_rows_hip(x: torch.Tensor, lens, plans, gain, frame_geom):
+    """Launch csrc/prosody.hip wsola_rows.  plans[b] is None (pass-through
+    row: copied and scaled) or a wsola_plan tuple; frame_geom = (frame, half,
+    search), shared by the batch.  Returns (y, targets, out_lengths)."""
+    from ..audio.window import hann_window
+
+    ext = hip_ext(required=True)
+    frame, half, search = frame_geom
+    dev = x.device
+    hop = [p[3] if p is not None else 1.0 for p in plans]
+    nfr = [p[4] if p is not None else 0 for p in plans]
+    out = [p[5] if p is not None else n for p, n in zip(plans, lens)]
+    # the host's own window, bit for bit (never recomputed on the device)
+    win = torch.from_numpy(hann_window(frame).copy()).to(dev)
+    y, targets = ext.wsola_rows(
+        x.contiguous(), _i32(lens, dev),
+        torch.tensor(hop, dtype=torch.float64, device=dev),
+        _i32(nfr, dev), _i32(out, dev), win, half, search,
+        torch.tensor(gain, dtype=torch.float32, device=dev),
+        max(out, default=0), max(max(nfr, default=0), 1))
+    return y, targets, torch.tensor(out, dtype=torch.long)
+
+
+def wsola_rows(x: torch.Tensor, lengths, sample_rate: int, speed, gain=None,
+               frame_ms: float = 30.0, search_ms: float = 10.0,
+               return_targets: bool = False):
+    """Per-row WSOLA time stretch of x [B, N] f32 (duration/speed[b], pitch
+    preserved), then a per-row gain.  Rows with |speed-1| < 1e-3, empty
+    rows and rows shorter than one frame are copied (and scaled).
+    Returns (y zero-padded, out_lengths[, targets [B, K] i32 — the start
+    of every analysis frame, -1 in unused slots; HIP path only])."""
+    from ..audio import prosody as P
+
+    B = x.shape[0]
+    lens = _row_lengths(lengths, B)
+    speeds = _per_row(speed, B)
+    gains = _per_row(gain, B)
+    frame, half, search = P.wsola_plan(0, 1.0, sample_rate, frame_ms,
+                                       search_ms)[:3]
+    if not use_hip(x):
+        import numpy as np
+
+        assert not return_targets, "targets are a HIP-path output"
+        xn = x.detach().cpu().numpy()
+        rows = []
+        for b in range(B):
+            r = xn[b, : lens[b]]
+            if P.wsola_is_passthrough(lens[b], speeds[b], frame):
+                r = r.copy()
+            else:
+                r = P.time_stretch_wsola(r, speeds[b], sample_rate,
+                                         frame_ms, search_ms)
+            if gains[b] != 1.0:
+                r = r * np.float32(gains[b])
+            rows.append(r)
+        return _rows_from_numpy(rows, x.device)
+    plans = [None if P.wsola_is_passthrough(n, s, frame)
+             else P.wsola_plan(n, s, sample_rate, frame_ms, search_ms)
+             for n, s in zip(lens, speeds)]
+    y, targets, out = _wsola_rows_hip(x, lens, plans, gains,
+                                      (frame, half, search))
+    return (y, out, targets) if return_targets else (y, out)
+
+
+def apply_prosody_rows(x: torch.Tensor, lengths, sample_rate: int,
+                       speed=None, volume=None, pitch=None):
+    """Batched audio.prosody.apply_prosody: x [B, N] f32 rows of
+    lengths[b] samples, per-row speed / volume / pitch.  Same composition
+    and thresholds: pitch = resample by pitch then stretch by 1/pitch; then
+    stretch by speed; then gain.  Returns (y [B, max out] zero-padded,
+    out_lengths).  The gain rides in the last kernel that runs; a
+    volume-only batch launches only a scale."""
+    from ..audio import prosody as P
+
+    B = x.shape[0]
+    lens = _row_lengths(lengths, B)
+    speeds, vols, pitches = (_per_row(speed, B), _per_row(volume, B),
+                             _per_row(pitch, B))
+    do_pitch = [abs(p - 1.0) >= 1e-3 for p in pitches]
+    do_speed = [abs(s - 1.0) >= 1e-3 for s in speeds]
+    do_gain = [abs(v - 1.0) >= 1e-6 for v in vols]
+    if not use_hip(x):
+        import numpy as np
+
+        frame = P.wsola_plan(0, 1.0, sample_rate)[0]
+
+        def stretch(r, s):
+            if P.wsola_is_passthrough(len(r), s, frame):
+                return r.copy()
+            return P.time_stretch_wsola(r, s, sample_rate)
+
+        xn = x.detach().cpu().numpy().astype(np.float32, copy=False)
+        rows = []
+        for b in range(B):
+            r = xn[b, : lens[b]]
+            if do_pitch[b]:
+                r = stretch(P.resample_linear(r, pitches[b]),
+                            1.0 / pitches[b])
+            if do_speed[b]:
+                r = stretch(r, speeds[b])
+            if do_gain[b]:
+                r = r * np.float32(vols[b])
+            rows.append(r)
+        return _rows_from_numpy(rows, x.device)
+
+    gains = [v if g else 1.0 for v, g in zip(vols, do_gain)]
+    ones = [1.0] * B
+    y, cur = x, lens
+    any_speed = any(do_speed)
+    if any(do_pitch):
+        y, out = resample_linear_rows(
+            y, cur, [p if d else 1.0 for p, d in zip(pitches, do_pitch)])
+        cur = out.tolist()
+        y, out = wsola_rows(
+            y, cur, sample_rate,
+            [1.0 / p if d else 1.0 for p, d in zip(pitches, do_pitch)],
+            gain=ones if any_speed else gains)
+        cur = out.tolist()
+    if any_speed:
+        y, out = wsola_rows(
+            y, cur, sample_rate,
+            [s if d else 1.0 for s, d in zip(speeds, do_speed)], gain=gains)
+        cur = out.tolist()
+    elif not any(do_pitch) and any(do_gain):
+        ext = hip_ext(required=True)
+        y = ext.scale_rows(
+            y.contiguous(), _i32(cur, y.device),
+            torch.tensor(gains, dtype=torch.float32, device=y.device))
+    return y, torch.tensor(cur, dtype=torch.long)

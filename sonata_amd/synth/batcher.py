@@ -16,7 +16,7 @@ from __future__ import annotations
 import queue
 import threading
 from concurrent.futures import Future
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence
 
 from ..core import Audio, SonataModel
 
@@ -27,18 +27,24 @@ class DynamicBatcher:
         self.model = model
         self.max_batch = max_batch
         self.max_wait = max_wait_ms / 1000.0
-        self._q: "queue.Queue[Optional[Tuple[str, Future]]]" = queue.Queue()
+        # items: (phonemes, future, prosody triple or None)
+        self._q: "queue.Queue[Optional[tuple]]" = queue.Queue()
         self._worker = threading.Thread(target=self._run, daemon=True,
                                         name="sonata_batcher")
         self._closed = False
         self._worker.start()
 
-    def submit(self, phonemes: str) -> "Future[Audio]":
-        """Queue one sentence; the future resolves with its Audio."""
+    def submit(self, phonemes: str,
+               prosody: Optional[Sequence[float]] = None) -> "Future[Audio]":
+        """Queue one sentence; the future resolves with its Audio.
+        `prosody`: optional (speed, volume, pitch) applied to this request's
+        row by the model (speak_batch(prosody=...)); rows of one batch may
+        each carry their own."""
         if self._closed:
             raise RuntimeError("batcher closed")
         f: "Future[Audio]" = Future()
-        self._q.put((phonemes, f))
+        self._q.put((phonemes, f, tuple(prosody) if prosody is not None
+                     else None))
         return f
 
     def synthesize(self, phonemes: str) -> Audio:
@@ -55,7 +61,7 @@ class DynamicBatcher:
             item = self._q.get()
             if item is None:
                 return
-            batch: List[Tuple[str, Future]] = [item]
+            batch: List[tuple] = [item]
             # drain whatever arrives within the wait window
             deadline = None
             while len(batch) < self.max_batch:
@@ -71,7 +77,7 @@ class DynamicBatcher:
                 deadline = 0.0  # after the first wait, drain non-blocking
             self._flush(batch)
 
-    def _flush(self, batch: List[Tuple[str, Future]]) -> None:
+    def _flush(self, batch: List[tuple]) -> None:
         # Length-bucketed sub-batches: padded batching costs compute
         # proportional to the LONGEST utterance, so a 3-word request
         # coalesced with a 40-word one would pay 10x.  Sort by length
@@ -84,13 +90,17 @@ class DynamicBatcher:
                 self._run_bucket(batch[start:i])
                 start = i
 
-    def _run_bucket(self, bucket: List[Tuple[str, Future]]) -> None:
-        phonemes = [p for p, _ in bucket]
+    def _run_bucket(self, bucket: List[tuple]) -> None:
+        phonemes = [it[0] for it in bucket]
+        prosody = [it[2] for it in bucket]
         try:
-            audios = self.model.speak_batch(phonemes)
-            for (_, f), audio in zip(bucket, audios):
+            if any(p is not None for p in prosody):
+                audios = self.model.speak_batch(phonemes, prosody=prosody)
+            else:
+                audios = self.model.speak_batch(phonemes)
+            for (_, f, _p), audio in zip(bucket, audios):
                 f.set_result(audio)
         except BaseException as e:  # noqa: BLE001 - propagate to callers
-            for _, f in bucket:
+            for _, f, _p in bucket:
                 if not f.done():
                     f.set_exception(e)

@@ -50,6 +50,18 @@ def synthesis_pool() -> ThreadPoolExecutor:
         return _POOL
 
 
+def device_prosody_enabled(model) -> bool:
+    """Device prosody is available for `model`: it advertises
+    supports_device_prosody, lives on cuda, and SONATA_DEVICE_PROSODY is
+    not 0."""
+    if os.environ.get("SONATA_DEVICE_PROSODY", "1") == "0":
+        return False
+    if not getattr(model, "supports_device_prosody", False):
+        return False
+    dev = getattr(model, "device", None)
+    return getattr(dev, "type", None) == "cuda"
+
+
 def _percent(value: float, lo: float, hi: float) -> float:
     v = min(max(value, 0.0), 100.0)
     return lo + (hi - lo) * (v / 100.0)
@@ -64,6 +76,19 @@ class AudioOutputConfig:
     volume: Optional[float] = None
     pitch: Optional[float] = None
     appended_silence_ms: Optional[float] = None
+
+    def prosody_triple(self):
+        """(speed, volume, pitch) as parameters (not percent) — what `apply`
+        hands to apply_prosody; the form speak_batch(prosody=...) takes."""
+        speed = _percent(self.rate, *RATE_RANGE) if self.rate is not None else 1.0
+        volume = (
+            _percent(self.volume, *VOLUME_RANGE)
+            if self.volume is not None else 1.0
+        )
+        pitch = (
+            _percent(self.pitch, *PITCH_RANGE) if self.pitch is not None else 1.0
+        )
+        return speed, volume, pitch
 
     def apply(self, samples: np.ndarray, sample_rate: int) -> np.ndarray:
         speed = _percent(self.rate, *RATE_RANGE) if self.rate is not None else 1.0
@@ -94,11 +119,28 @@ class SonataSpeechSynthesizer:
     def audio_output_info(self) -> AudioInfo:
         return self.model.audio_output_info()
 
-    def _post(self, audio: Audio, cfg: Optional[AudioOutputConfig]) -> Audio:
+    def device_prosody(self, cfg: Optional[AudioOutputConfig]) -> bool:
+        """True when `cfg`'s rate / volume / pitch run on the device inside
+        speak_batch: the model offers it, lives on cuda, and
+        SONATA_DEVICE_PROSODY is not 0 (0 = host prosody, for A/B runs)."""
+        return device_prosody_enabled(self.model) and cfg is not None \
+            and not cfg.is_noop
+
+    def _speak_device_prosody(self, sentences: List[str],
+                              cfg: AudioOutputConfig) -> List[Audio]:
+        """One speak_batch with cfg's prosody applied on the device; _post
+        then only appends silence."""
+        triple = cfg.prosody_triple()
+        batch = self.model.speak_batch(
+            sentences, prosody=[triple] * len(sentences))
+        return [self._post(a, cfg, prosody_done=True) for a in batch]
+
+    def _post(self, audio: Audio, cfg: Optional[AudioOutputConfig],
+              prosody_done: bool = False) -> Audio:
         if cfg is None:
             return audio
         samples = audio.samples
-        if not cfg.is_noop:
+        if not cfg.is_noop and not prosody_done:
             samples = cfg.apply(samples, audio.info.sample_rate)
         if cfg.appended_silence_ms:
             samples = merge(
@@ -116,6 +158,9 @@ class SonataSpeechSynthesizer:
         (reference SonataSpeechStreamLazy, synth/src/lib.rs:282-307)."""
         phonemes = self.model.phonemize_text(text)
         for sent in phonemes:
+            if self.device_prosody(output_config):
+                yield self._speak_device_prosody([sent], output_config)[0]
+                continue
             yield self._post(self.model.speak_one_sentence(sent), output_config)
 
     def synthesize_parallel(
@@ -127,6 +172,9 @@ class SonataSpeechSynthesizer:
         phonemes = self.model.phonemize_text(text)
         if len(phonemes) == 0:
             return iter(())
+        if self.device_prosody(output_config):
+            return iter(self._speak_device_prosody(list(phonemes),
+                                                   output_config))
         batch = self.model.speak_batch(list(phonemes))
         return iter([self._post(a, output_config) for a in batch])
 
