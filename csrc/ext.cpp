@@ -91,6 +91,10 @@ std::vector<torch::Tensor> wsola_rows(torch::Tensor x, torch::Tensor in_len,
                                       torch::Tensor window, long half,
                                       long search, torch::Tensor gain,
                                       long N_out_max, long K_max);
+// pcm.hip
+std::vector<torch::Tensor> pcm16_rows(torch::Tensor x, torch::Tensor len,
+                                      long N_out, bool peak_normalize);
+long pcm_tile();
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "sonata_amd hand-written CDNA4 (gfx950) kernels";
@@ -138,6 +142,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n_frames"), py::arg("out_len"), py::arg("window"),
         py::arg("half"), py::arg("search"), py::arg("gain"),
         py::arg("n_out_max"), py::arg("k_max"));
+  m.def("pcm16_rows", &pcm16_rows,
+        "per-row peak-normalised int16 PCM of [B,N] f32/bf16; returns "
+        "(pcm [B,n_out], peaks)",
+        py::arg("x"), py::arg("len"), py::arg("n_out"),
+        py::arg("peak_normalize") = true);
+  m.attr("PCM_TILE") = pcm_tile();
 
   // C++ inference runtime (csrc/engine): the ort-replacement executor.
   py::class_<sonata::VitsEngine>(m, "VitsEngine")

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         "csrc/resblock_cl.hip",
         "csrc/attention_cl.hip",
         "csrc/prosody.hip",
+        "csrc/pcm.hip",
         "csrc/engine/vits_engine.cpp",
     ],
     extra_compile_args={

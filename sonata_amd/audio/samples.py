@@ -130,6 +130,10 @@ def to_decibel(samples) -> np.ndarray:
     return (20.0 * np.log10(np.maximum(np.abs(s), 1e-10))).astype(np.float32)
 
 
+def silence_samples(ms: float, sample_rate: int) -> int:
+    """Length of generate_silence(ms, sample_rate) in samples."""
+    return max(int(round(ms * sample_rate / 1000.0)), 0)
+
+
 def generate_silence(ms: float, sample_rate: int) -> np.ndarray:
-    n = int(round(ms * sample_rate / 1000.0))
-    return np.zeros(max(n, 0), dtype=np.float32)
+    return np.zeros(silence_samples(ms, sample_rate), dtype=np.float32)

@@ -29,7 +29,14 @@ def wav_header(data_bytes: int, sample_rate: int, num_channels: int = 1,
 
 def wav_bytes(samples, sample_rate: int, num_channels: int = 1,
               peak_normalize: bool = True) -> bytes:
-    pcm = to_i16(samples, peak_normalize=peak_normalize).astype("<i2").tobytes()
+    return wav_bytes_pcm(to_i16(samples, peak_normalize=peak_normalize),
+                         sample_rate, num_channels)
+
+
+def wav_bytes_pcm(pcm, sample_rate: int, num_channels: int = 1) -> bytes:
+    """WAV file bytes for int16 samples that are already PCM (what
+    wav_bytes writes for the float samples they came from)."""
+    pcm = np.asarray(pcm, dtype=np.int16).reshape(-1).astype("<i2").tobytes()
     byte_rate = sample_rate * num_channels * 2
     block_align = num_channels * 2
     buf = io.BytesIO()
@@ -49,6 +56,12 @@ def write_wav_file(path: str, samples, sample_rate: int,
                    num_channels: int = 1) -> None:
     with open(path, "wb") as f:
         f.write(wav_bytes(samples, sample_rate, num_channels))
+
+
+def write_wav_file_pcm(path: str, pcm, sample_rate: int,
+                       num_channels: int = 1) -> None:
+    with open(path, "wb") as f:
+        f.write(wav_bytes_pcm(pcm, sample_rate, num_channels))
 
 
 def read_wav_file(path: str):

@@ -106,6 +106,51 @@ class Audio:
         write_wav_file(path, self.samples, self.info.sample_rate)
 
 
+@dataclass
+class PcmAudio:
+    """A synthesized waveform already converted to wire format: `pcm` is
+    the peak-normalised int16 that `Audio.as_wave_bytes` would produce for
+    the float samples it came from (converted on the device by
+    speak_batch_pcm when available).  Offers front ends what Audio does."""
+
+    pcm: np.ndarray
+    info: AudioInfo
+    inference_ms: float = 0.0
+
+    def __post_init__(self):
+        self.pcm = np.asarray(self.pcm, dtype=np.int16).reshape(-1)
+
+    @classmethod
+    def from_audio(cls, audio: Audio, silence_samples: int = 0) -> "PcmAudio":
+        """Host conversion: to_i16 of audio.samples followed by
+        `silence_samples` zeros (equal to to_i16 of the samples with that
+        silence merged: zeros neither move the peak nor scale)."""
+        from .audio.samples import to_i16
+
+        pcm = to_i16(audio.samples)
+        if silence_samples > 0:
+            pcm = np.concatenate(
+                [pcm, np.zeros(silence_samples, dtype=np.int16)])
+        return cls(pcm, audio.info, audio.inference_ms)
+
+    @property
+    def duration_ms(self) -> float:
+        return len(self.pcm) * 1000.0 / self.info.sample_rate
+
+    @property
+    def real_time_factor(self) -> float:
+        d = self.duration_ms
+        return (self.inference_ms / d) if d > 0 else 0.0
+
+    def as_wave_bytes(self) -> bytes:
+        return self.pcm.astype("<i2", copy=False).tobytes()
+
+    def save_to_file(self, path: str) -> None:
+        from .audio.wav import write_wav_file_pcm
+
+        write_wav_file_pcm(path, self.pcm, self.info.sample_rate)
+
+
 # --------------------------------------------------------------------------- #
 # Model interface (reference: core/src/lib.rs:82-131 trait SonataModel)
 # --------------------------------------------------------------------------- #
@@ -132,6 +177,12 @@ class SonataModel(abc.ABC):
         """True padded batching (the reference's speak_batch loops batch=1,
         piper/src/lib.rs:425-437 — here a real [B, T] batch is the default)."""
         return [self.speak_one_sentence(p) for p in phonemes_batch]
+
+    @property
+    def supports_device_pcm(self) -> bool:
+        """True when the model offers speak_batch_pcm(phonemes_batch,
+        prosody=None, silence_ms=None) -> List[PcmAudio]."""
+        return False
 
     # -- synthesis config (reference get/set_fallback..., typed not Any) ---- #
     @abc.abstractmethod

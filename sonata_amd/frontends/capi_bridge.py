@@ -76,10 +76,10 @@ def speak_chunks(synth, text: str, mode: int, rate: int, volume: int,
                 text, out_cfg, REALTIME_CHUNK_SIZE, REALTIME_CHUNK_PADDING):
             yield to_i16_bytes(chunk)
     elif mode == MODE_LAZY:
-        for audio in synth.synthesize_lazy(text, out_cfg):
+        for audio in synth.synthesize_lazy(text, out_cfg, pcm=True):
             yield audio.as_wave_bytes()
     else:
-        for audio in synth.synthesize_parallel(text, out_cfg):
+        for audio in synth.synthesize_parallel(text, out_cfg, pcm=True):
             yield audio.as_wave_bytes()
 
 

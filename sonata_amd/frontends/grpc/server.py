@@ -197,7 +197,7 @@ class SonataGrpcService:
             request.speech_args if request.HasField("speech_args") else None)
         mode = request.synthesis_mode
         if mode == MODE_LAZY:
-            it = v.synth.synthesize_lazy(request.text, out_cfg)
+            it = v.synth.synthesize_lazy(request.text, out_cfg, pcm=True)
             for audio in it:
                 yield MESSAGES["SynthesisResult"](
                     wav_samples=audio.as_wave_bytes(),
@@ -211,11 +211,17 @@ class SonataGrpcService:
         # the device path is on; _post then only appends silence
         on_device = v.synth.device_prosody(out_cfg)
         triple = out_cfg.prosody_triple() if on_device else None
-        futures = [v.batcher.submit(sent, triple) for sent in sentences]
+        # the batch comes back as int16 PCM (converted on the device when
+        # the voice can) unless prosody has to run on the host's floats
+        pcm = out_cfg is None or out_cfg.is_noop or on_device
+        silence_ms = out_cfg.appended_silence_ms if out_cfg else None
+        futures = [v.batcher.submit(sent, triple, pcm=pcm,
+                                    silence_ms=silence_ms if pcm else None)
+                   for sent in sentences]
         for f in futures:
             audio = f.result()
-            if out_cfg is not None:
-                audio = v.synth._post(audio, out_cfg, prosody_done=on_device)
+            if not pcm:
+                audio = v.synth.to_pcm(audio, out_cfg)
             yield MESSAGES["SynthesisResult"](
                 wav_samples=audio.as_wave_bytes(),
                 rtf=float(audio.real_time_factor),

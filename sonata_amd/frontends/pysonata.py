@@ -164,14 +164,14 @@ class Sonata:
                         audio_output_config: Optional[AudioOutputConfig]
                         = None) -> Iterator[WaveSamples]:
         cfg = audio_output_config._to_internal() if audio_output_config else None
-        for a in self._synth.synthesize_lazy(text, cfg):
+        for a in self._synth.synthesize_lazy(text, cfg, pcm=True):
             yield WaveSamples(a)
 
     def synthesize_parallel(self, text: str,
                             audio_output_config: Optional[AudioOutputConfig]
                             = None) -> Iterator[WaveSamples]:
         cfg = audio_output_config._to_internal() if audio_output_config else None
-        for a in self._synth.synthesize_parallel(text, cfg):
+        for a in self._synth.synthesize_parallel(text, cfg, pcm=True):
             yield WaveSamples(a)
 
     def synthesize_streamed(self, text: str,

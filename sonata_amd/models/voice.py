@@ -21,9 +21,10 @@ from typing import Dict, Iterator, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ..audio.samples import crossfade
+from ..audio.samples import crossfade, silence_samples
 from ..utils.trace import stage_timer
-from ..core import Audio, AudioInfo, ModelError, Phonemes, SonataModel
+from ..core import (Audio, AudioInfo, ModelError, PcmAudio, Phonemes,
+                    SonataModel)
 from ..text.ids import phonemes_to_ids
 from ..text.phonemizer import text_to_phonemes
 from .chunker import chunk_plan
@@ -159,13 +160,10 @@ class VitsVoice(SonataModel):
         return y.unsqueeze(1), out_lengths
 
     @torch.no_grad()
-    def speak_batch(self, phonemes_batch: Sequence[str],
-                    prosody=None) -> List[Audio]:
-        """True padded [B, T] batching (the reference loops batch=1:
-        piper/src/lib.rs:425-437 — batching is a headline improvement).
-
-        `prosody`: optional per-row sequence of (speed, volume, pitch) or
-        None; applied on the device tensor before the single host copy."""
+    def _infer_batch(self, phonemes_batch: Sequence[str]):
+        """Id-encode and run one padded batch.  Returns the decoder output
+        [B, 1, T] and per-row lengths, both on the model's device, and the
+        wall time of the inference in ms."""
         cfg = self.get_synthesis_config()
         id_lists = [self._encode_ids(p) for p in phonemes_batch]
         B = len(id_lists)
@@ -191,18 +189,7 @@ class VitsVoice(SonataModel):
                 if self.device.type == "cuda":
                     torch.cuda.synchronize(self.device)
             infer_ms = (time.perf_counter() - t0) * 1000.0
-            info = self.audio_output_info()
-            out: List[Audio] = []
-            if prosody is not None:
-                audio, audio_lengths = self._prosody_rows(
-                    audio, audio_lengths, prosody)
-            audio = audio.float().cpu().numpy()
-            audio_lengths = audio_lengths.cpu().numpy()
-            for b in range(B):
-                n = int(audio_lengths[b])
-                out.append(Audio(audio[b, 0, :n], info,
-                                 inference_ms=infer_ms / B))
-            return out
+            return audio, audio_lengths, infer_ms
         with self._infer_lock, stage_timer("infer", self.device):
             audio, audio_lengths = self.net.infer(
             ids,
@@ -216,7 +203,18 @@ class VitsVoice(SonataModel):
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         infer_ms = (time.perf_counter() - t0) * 1000.0
+        return audio, audio_lengths, infer_ms
 
+    @torch.no_grad()
+    def speak_batch(self, phonemes_batch: Sequence[str],
+                    prosody=None) -> List[Audio]:
+        """True padded [B, T] batching (the reference loops batch=1:
+        piper/src/lib.rs:425-437 — batching is a headline improvement).
+
+        `prosody`: optional per-row sequence of (speed, volume, pitch) or
+        None; applied on the device tensor before the single host copy."""
+        audio, audio_lengths, infer_ms = self._infer_batch(phonemes_batch)
+        B = len(phonemes_batch)
         info = self.audio_output_info()
         out: List[Audio] = []
         if prosody is not None:
@@ -228,6 +226,51 @@ class VitsVoice(SonataModel):
             n = int(audio_lengths[b])
             out.append(Audio(audio[b, 0, :n], info, inference_ms=infer_ms / B))
         return out
+
+    @property
+    def supports_device_pcm(self) -> bool:
+        """speak_batch_pcm converts the batch to int16 PCM on the model's
+        device (when it is a GPU), before the copy to the host."""
+        return True
+
+    def _device_pcm(self) -> bool:
+        return (self.device.type == "cuda"
+                and os.environ.get("SONATA_DEVICE_PCM", "1") != "0")
+
+    @torch.no_grad()
+    def speak_batch_pcm(self, phonemes_batch: Sequence[str], prosody=None,
+                        silence_ms=None) -> List[PcmAudio]:
+        """speak_batch whose results are wire-format int16: what
+        `Audio.as_wave_bytes` gives for speak_batch's samples with
+        `silence_ms` of silence merged on (per row or one value; rounded to
+        samples as generate_silence does).  On cuda the order is optional
+        device prosody, ops.pcm16_rows, then ONE host copy of the int16
+        batch: half the bytes of the float copy, and no per-row NumPy
+        passes.  A CPU voice, or SONATA_DEVICE_PCM=0, converts
+        speak_batch's samples on the host: same bytes."""
+        B = len(phonemes_batch)
+        if silence_ms is None or isinstance(silence_ms, (int, float)):
+            silence_ms = [silence_ms] * B
+        assert len(silence_ms) == B, "one silence value per row"
+        sil = [silence_samples(ms, self.config.sample_rate) if ms else 0
+               for ms in silence_ms]
+        if not self._device_pcm():
+            audios = (self.speak_batch(phonemes_batch, prosody=prosody)
+                      if prosody is not None
+                      else self.speak_batch(phonemes_batch))
+            return [PcmAudio.from_audio(a, s) for a, s in zip(audios, sil)]
+        from ..ops import pcm16_rows
+
+        audio, audio_lengths, infer_ms = self._infer_batch(phonemes_batch)
+        if prosody is not None:
+            audio, audio_lengths = self._prosody_rows(
+                audio, audio_lengths, prosody)
+        # bf16 decoder output is read as it is (widening is exact)
+        pcm, out_lengths = pcm16_rows(audio[:, 0, :], audio_lengths, sil)
+        pcm = pcm.cpu().numpy()
+        info = self.audio_output_info()
+        return [PcmAudio(pcm[b, : int(out_lengths[b])], info,
+                         inference_ms=infer_ms / B) for b in range(B)]
 
     # ------------------------------------------------------------------ #
     # streaming decode (encoder once, HiFi-GAN chunked)

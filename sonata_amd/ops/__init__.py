@@ -74,4 +74,5 @@ from .functional import (  # noqa: F401,E402
     resample_linear_rows,
     wsola_rows,
     apply_prosody_rows,
+    pcm16_rows,
 )

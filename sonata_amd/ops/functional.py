@@ -764,3 +764,59 @@ def apply_prosody_rows(x: torch.Tensor, lengths, sample_rate: int,
             y.contiguous(), _i32(cur, y.device),
             torch.tensor(gains, dtype=torch.float32, device=y.device))
     return y, torch.tensor(cur, dtype=torch.long)
+
+
+# --------------------------------------------------------------------------- #
+# batched PCM: [B, N] f32 / bf16 rows -> peak-normalised int16 with per-row
+# lengths and appended silence (csrc/pcm.hip).  The CPU path calls
+# audio.samples.to_i16 row by row and is the oracle; the kernels match it
+# bit for bit.
+# --------------------------------------------------------------------------- #
+PCM_TILE = 4096  # elements per workgroup of the peak kernel (csrc/pcm.hip)
+
+
+def _per_row_int(v, B: int):
+    if v is None:
+        return [0] * B
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().tolist()
+    if isinstance(v, (int, float)):
+        return [int(v)] * B
+    out = [int(t) for t in v]
+    assert len(out) == B, "one parameter per row"
+    return out
+
+
+def pcm16_rows(x: torch.Tensor, lengths, silence=None,
+               peak_normalize: bool = True):
+    """int16 PCM of x [B, N] (f32 or bf16) rows of lengths[b] samples, as
+    audio.samples.to_i16 gives it: scale = 32767/peak of the row (0 for a
+    peak <= 1e-8; 32767 without peak_normalize), clamp, truncate.  `silence`
+    (samples, per row or one int) is appended as zeros.  Returns
+    (pcm int16 [B, N_out], out_lengths) with out_lengths[b] = lengths[b] +
+    silence[b] and N_out = max(out_lengths) rounded up to a multiple of 8
+    (aligned rows); columns past lengths[b] are 0."""
+    B = x.shape[0]
+    lens = _row_lengths(lengths, B)
+    assert all(0 <= n <= x.shape[1] for n in lens), "length outside the row"
+    sil = _per_row_int(silence, B)
+    assert all(s >= 0 for s in sil), "negative silence"
+    out = [n + s for n, s in zip(lens, sil)]
+    n_out = _round_up(max(out, default=0), 8)
+    out_lengths = torch.tensor(out, dtype=torch.long)
+    if not use_hip(x):
+        import numpy as np
+
+        from ..audio.samples import to_i16
+
+        xn = x.detach().float().cpu().numpy()
+        y = np.zeros((B, n_out), dtype=np.int16)
+        for b in range(B):
+            y[b, : lens[b]] = to_i16(xn[b, : lens[b]], peak_normalize)
+        return torch.from_numpy(y).to(x.device), out_lengths
+    ext = hip_ext(required=True)
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    pcm, _peaks = ext.pcm16_rows(x, _i32(lens, x.device), n_out,
+                                 bool(peak_normalize))
+    return pcm, out_lengths

@@ -18,7 +18,8 @@ import threading
 from concurrent.futures import Future
 from typing import List, Optional, Sequence
 
-from ..core import Audio, SonataModel
+from ..audio.samples import silence_samples
+from ..core import Audio, PcmAudio, SonataModel
 
 
 class DynamicBatcher:
@@ -27,7 +28,8 @@ class DynamicBatcher:
         self.model = model
         self.max_batch = max_batch
         self.max_wait = max_wait_ms / 1000.0
-        # items: (phonemes, future, prosody triple or None)
+        # items: (phonemes, future, prosody triple or None, pcm,
+        #         silence_ms or None)
         self._q: "queue.Queue[Optional[tuple]]" = queue.Queue()
         self._worker = threading.Thread(target=self._run, daemon=True,
                                         name="sonata_batcher")
@@ -35,16 +37,23 @@ class DynamicBatcher:
         self._worker.start()
 
     def submit(self, phonemes: str,
-               prosody: Optional[Sequence[float]] = None) -> "Future[Audio]":
+               prosody: Optional[Sequence[float]] = None,
+               pcm: bool = False,
+               silence_ms: Optional[float] = None) -> "Future[Audio]":
         """Queue one sentence; the future resolves with its Audio.
         `prosody`: optional (speed, volume, pitch) applied to this request's
         row by the model (speak_batch(prosody=...)); rows of one batch may
-        each carry their own."""
+        each carry their own.
+        `pcm=True`: the future resolves with a PcmAudio (wire-format int16)
+        with `silence_ms` of silence appended.  A bucket whose requests all
+        want PCM runs one speak_batch_pcm; in a mixed bucket the PCM rows
+        are converted on the host.  The bytes are the same either way."""
         if self._closed:
             raise RuntimeError("batcher closed")
+        assert pcm or not silence_ms, "silence_ms rides with pcm requests"
         f: "Future[Audio]" = Future()
         self._q.put((phonemes, f, tuple(prosody) if prosody is not None
-                     else None))
+                     else None, bool(pcm), silence_ms))
         return f
 
     def synthesize(self, phonemes: str) -> Audio:
@@ -93,14 +102,26 @@ class DynamicBatcher:
     def _run_bucket(self, bucket: List[tuple]) -> None:
         phonemes = [it[0] for it in bucket]
         prosody = [it[2] for it in bucket]
+        kw = {"prosody": prosody} if any(
+            p is not None for p in prosody) else {}
         try:
-            if any(p is not None for p in prosody):
-                audios = self.model.speak_batch(phonemes, prosody=prosody)
+            if all(it[3] for it in bucket) and getattr(
+                    self.model, "supports_device_pcm", False):
+                audios = self.model.speak_batch_pcm(
+                    phonemes, silence_ms=[it[4] for it in bucket], **kw)
             else:
-                audios = self.model.speak_batch(phonemes)
-            for (_, f, _p), audio in zip(bucket, audios):
-                f.set_result(audio)
+                audios = self.model.speak_batch(phonemes, **kw)
+                audios = [self._host_pcm(a, it[4]) if it[3] else a
+                          for it, a in zip(bucket, audios)]
+            for it, audio in zip(bucket, audios):
+                it[1].set_result(audio)
         except BaseException as e:  # noqa: BLE001 - propagate to callers
-            for _, f, _p in bucket:
-                if not f.done():
-                    f.set_exception(e)
+            for it in bucket:
+                if not it[1].done():
+                    it[1].set_exception(e)
+
+    @staticmethod
+    def _host_pcm(audio: Audio, silence_ms: Optional[float]) -> PcmAudio:
+        sil = (silence_samples(silence_ms, audio.info.sample_rate)
+               if silence_ms else 0)
+        return PcmAudio.from_audio(audio, sil)

@@ -24,9 +24,9 @@ from typing import Iterator, List, Optional
 import numpy as np
 
 from ..audio.prosody import apply_prosody
-from ..audio.samples import generate_silence, merge
+from ..audio.samples import generate_silence, merge, silence_samples
 from ..audio.wav import write_wav_file
-from ..core import Audio, AudioInfo, SonataModel
+from ..core import Audio, AudioInfo, PcmAudio, SonataModel
 
 # percent(0-100) -> parameter ranges (reference synth/src/lib.rs:13-15)
 RATE_RANGE = (0.5, 5.5)
@@ -150,28 +150,71 @@ class SonataSpeechSynthesizer:
             )
         return Audio(samples, audio.info, audio.inference_ms)
 
+    def _speak_pcm(self, sentences: List[str],
+                   cfg: Optional[AudioOutputConfig]) -> List[PcmAudio]:
+        """One batch as wire-format PcmAudio, bytes equal to
+        as_wave_bytes() of the float path.  A model with speak_batch_pcm
+        gets prosody (when the device path is on), appended silence and the
+        int16 conversion in that one call; it decides itself between the
+        device and the host conversion (SONATA_DEVICE_PCM).  Prosody that
+        has to run on the host keeps the float path up to the conversion."""
+        host_prosody = (cfg is not None and not cfg.is_noop
+                        and not self.device_prosody(cfg))
+        if getattr(self.model, "supports_device_pcm", False) \
+                and not host_prosody:
+            triple = (cfg.prosody_triple()
+                      if cfg is not None and not cfg.is_noop else None)
+            return self.model.speak_batch_pcm(
+                sentences,
+                prosody=[triple] * len(sentences) if triple else None,
+                silence_ms=cfg.appended_silence_ms if cfg else None)
+        batch = self.model.speak_batch(sentences)
+        return [self.to_pcm(a, cfg) for a in batch]
+
+    def to_pcm(self, audio: Audio, cfg: Optional[AudioOutputConfig],
+               prosody_done: bool = False) -> PcmAudio:
+        """Host finish of one float result: prosody unless done, then the
+        int16 conversion with cfg's silence appended."""
+        if cfg is not None and not cfg.is_noop and not prosody_done:
+            audio = Audio(cfg.apply(audio.samples, audio.info.sample_rate),
+                          audio.info, audio.inference_ms)
+        sil = (silence_samples(cfg.appended_silence_ms,
+                               audio.info.sample_rate)
+               if cfg is not None and cfg.appended_silence_ms else 0)
+        return PcmAudio.from_audio(audio, sil)
+
     # ------------------------------------------------------------------ #
     def synthesize_lazy(
-        self, text: str, output_config: Optional[AudioOutputConfig] = None
+        self, text: str, output_config: Optional[AudioOutputConfig] = None,
+        pcm: bool = False,
     ) -> Iterator[Audio]:
         """Pull-based: each sentence synthesized when consumed
-        (reference SonataSpeechStreamLazy, synth/src/lib.rs:282-307)."""
+        (reference SonataSpeechStreamLazy, synth/src/lib.rs:282-307).
+        `pcm=True` yields PcmAudio (int16, converted on the device when the
+        model can) instead of float Audio; the wire bytes are the same."""
         phonemes = self.model.phonemize_text(text)
         for sent in phonemes:
+            if pcm:
+                yield self._speak_pcm([sent], output_config)[0]
+                continue
             if self.device_prosody(output_config):
                 yield self._speak_device_prosody([sent], output_config)[0]
                 continue
             yield self._post(self.model.speak_one_sentence(sent), output_config)
 
     def synthesize_parallel(
-        self, text: str, output_config: Optional[AudioOutputConfig] = None
+        self, text: str, output_config: Optional[AudioOutputConfig] = None,
+        pcm: bool = False,
     ) -> Iterator[Audio]:
         """Eager batched synthesis of all sentences.  The reference fans
         out per-sentence rayon tasks (synth/src/lib.rs:316-320); here the
-        model's true padded batch path does the fan-out on-device."""
+        model's true padded batch path does the fan-out on-device.
+        `pcm=True` yields PcmAudio, as in synthesize_lazy."""
         phonemes = self.model.phonemize_text(text)
         if len(phonemes) == 0:
             return iter(())
+        if pcm:
+            return iter(self._speak_pcm(list(phonemes), output_config))
         if self.device_prosody(output_config):
             return iter(self._speak_device_prosody(list(phonemes),
                                                    output_config))
