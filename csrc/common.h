@@ -8,6 +8,8 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
+#include <cstdint>
+
 #define WAVE 64
 
 using bf16 = __hip_bfloat16;
@@ -34,6 +36,38 @@ __device__ __forceinline__ float sigmoidf_(float x) {
 
 __device__ __forceinline__ float lrelu_(float x, float slope) {
   return x > 0.0f ? x : x * slope;
+}
+
+// Zero n bf16 elements from p with all nthreads threads of the block.  No
+// alignment is assumed beyond the element's own: the span is split by
+// ADDRESS into a scalar head up to the next 16-byte boundary, a body of
+// 16-byte stores and a scalar tail (the split pcm16_rows makes).
+__device__ __forceinline__ void zero_span_bf16(bf16* p, long n, int tid,
+                                               int nthreads) {
+  unsigned short* q = reinterpret_cast<unsigned short*>(p);
+  const long mis = (long)((reinterpret_cast<uintptr_t>(q) >> 1) & 7);
+  const long head = min(n, (8 - mis) & 7);
+  const long nvec = (n - head) >> 3;
+  const long tail0 = head + (nvec << 3);
+  if (tid < head) q[tid] = 0;
+  ulonglong2* body = reinterpret_cast<ulonglong2*>(q + head);
+  for (long v = tid; v < nvec; v += nthreads) body[v] = make_ulonglong2(0, 0);
+  if (tail0 + tid < n) q[tail0 + tid] = 0;
+}
+
+// Dead-tile fill of the channel-last kernels: zero rows [0, nrows) x
+// columns [c0, c0+ncols) of a [.][pitch] bf16 image whose row 0 starts at
+// base.  A tile that spans whole rows is one contiguous span; a column
+// tile (Cout wider than the block's BN) is one span per row, a wave each.
+__device__ __forceinline__ void zero_tile_bf16(bf16* base, long nrows,
+                                               int pitch, int c0, int ncols,
+                                               int tid, int nthreads) {
+  if (ncols == pitch) {
+    zero_span_bf16(base, nrows * pitch, tid, nthreads);
+    return;
+  }
+  for (long r = tid / WAVE; r < nrows; r += nthreads / WAVE)
+    zero_span_bf16(base + r * pitch + c0, ncols, tid % WAVE, WAVE);
 }
 
 #define HIP_CHECK(expr)                                                     \

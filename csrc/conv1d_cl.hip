@@ -53,6 +53,15 @@ __global__ __launch_bounds__(512) void conv1d_cl_kernel(
   const long t0 = (long)blockIdx.x * BM;
   const int n0 = blockIdx.y * BN;
   const int b = blockIdx.z;
+  const long lim = out_lens ? min((long)out_lens[b], Tout) : Tout;
+  // dead tile (all rows in the batch padding; uniform over the block, ahead
+  // of any barrier): store the epilogue's zeros and read nothing
+  if (t0 >= lim) {
+    zero_tile_bf16(out + ((long)b * Tout + t0) * Cout,
+                   min(t0 + BM, Tout) - t0, Cout, n0, min(BN, Cout - n0),
+                   threadIdx.x, 512);
+    return;
+  }
 
   __shared__ bf16 Xs[ROWS][BKP];
   __shared__ bf16 Ws[TC][BN][BKP];
@@ -173,7 +182,6 @@ __global__ __launch_bounds__(512) void conv1d_cl_kernel(
   // ---- epilogue: bias + act (+ residual) + ragged mask + store -------
   bf16* ob = out + (long)b * Tout * Cout;
   const bf16* rb = resid ? resid + (long)b * Tout * Cout : nullptr;
-  const long lim = out_lens ? min((long)out_lens[b], Tout) : Tout;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
 #pragma unroll
@@ -222,6 +230,15 @@ __global__ __launch_bounds__(512) void conv1d_cl_wdirect_kernel(
   const long t0 = (long)blockIdx.x * BM;
   const int n0 = blockIdx.y * BN;
   const int b = blockIdx.z;
+  const long lim = out_lens ? min((long)out_lens[b], Tout) : Tout;
+  // dead tile (all rows in the batch padding; uniform over the block, ahead
+  // of any barrier): store the epilogue's zeros and read nothing
+  if (t0 >= lim) {
+    zero_tile_bf16(out + ((long)b * Tout + t0) * Cout,
+                   min(t0 + BM, Tout) - t0, Cout, n0, min(BN, Cout - n0),
+                   threadIdx.x, 512);
+    return;
+  }
 
   __shared__ bf16 Xs[ROWS][BKP];
 
@@ -327,7 +344,6 @@ __global__ __launch_bounds__(512) void conv1d_cl_wdirect_kernel(
 
   bf16* ob = out + (long)b * Tout * Cout;
   const bf16* rb = resid ? resid + (long)b * Tout * Cout : nullptr;
-  const long lim = out_lens ? min((long)out_lens[b], Tout) : Tout;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
 #pragma unroll
@@ -373,6 +389,19 @@ __global__ __launch_bounds__(512) void convt1d_cl_kernel(
   const long v0 = (long)blockIdx.x * BMV;
   const int n0 = blockIdx.y * BN;
   const int b = blockIdx.z;
+  const long lim = out_lens ? min((long)out_lens[b], Tout) : Tout;
+  // dead tile: the block's out rows are [v0*S - pad, vend*S - pad) clipped
+  // to [0, Tout); all of them in the batch padding -> zeros, no reads
+  // (uniform over the block, ahead of any barrier)
+  {
+    const long tb = max(v0 * S - pad, 0L);
+    if (tb >= lim) {
+      const long te = min(min(v0 + BMV, Vn) * S - pad, Tout);
+      zero_tile_bf16(out + ((long)b * Tout + tb) * Cout, max(te - tb, 0L),
+                     Cout, n0, min(BN, Cout - n0), threadIdx.x, 512);
+      return;
+    }
+  }
 
   __shared__ bf16 Xs[ROWS][BKP];
   __shared__ bf16 Ws[TAUC][BN][BKP];
@@ -496,7 +525,6 @@ __global__ __launch_bounds__(512) void convt1d_cl_kernel(
 
   // ---- epilogue: per (v-row, phase) store out[v*S + r - pad][co] -----
   bf16* ob = out + (long)b * Tout * Cout;
-  const long lim = out_lens ? min((long)out_lens[b], Tout) : Tout;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
 #pragma unroll
@@ -718,6 +746,15 @@ __global__ __launch_bounds__(512) void conv1d_direct_cl_kernel(
   const long t0 = (long)blockIdx.x * BM;
   const int n0 = blockIdx.y * BN;
   const int b = blockIdx.z;
+  const long lim = out_lens ? min((long)out_lens[b], Tout) : Tout;
+  // dead tile (all rows in the batch padding; uniform over the block, ahead
+  // of any barrier): store the epilogue's zeros and read nothing
+  if (t0 >= lim) {
+    zero_tile_bf16(out + ((long)b * Tout + t0) * Cout,
+                   min(t0 + BM, Tout) - t0, Cout, n0, min(BN, Cout - n0),
+                   threadIdx.x, 512);
+    return;
+  }
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -779,7 +816,6 @@ __global__ __launch_bounds__(512) void conv1d_direct_cl_kernel(
 
   bf16* ob = out + (long)b * Tout * Cout;
   const bf16* rb = resid ? resid + (long)b * Tout * Cout : nullptr;
-  const long lim = out_lens ? min((long)out_lens[b], Tout) : Tout;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
 #pragma unroll

@@ -55,6 +55,12 @@ torch::Tensor resblock_pair_cl_fused(torch::Tensor x, torch::Tensor w1_perm,
                                      c10::optional<torch::Tensor> out_lens,
                                      c10::optional<torch::Tensor> accum,
                                      double out_scale);
+bool resblock_wlayout_sliced(long CP);
+torch::Tensor resblock_pair_cl_fused_sliced(
+    torch::Tensor x, torch::Tensor w1_sliced, torch::Tensor b1,
+    torch::Tensor w2_sliced, torch::Tensor b2, long k, long dil,
+    c10::optional<torch::Tensor> out_lens, c10::optional<torch::Tensor> accum,
+    double out_scale);
 torch::Tensor resblock_chain_cl_fused(
     torch::Tensor x, torch::Tensor w_all, torch::Tensor b_all, long k,
     long d1, long d2, long d3, c10::optional<torch::Tensor> out_lens,
@@ -242,6 +248,19 @@ torch::Tensor VitsEngine::perm_conv(const std::string& wname) const {
   pm = pm.contiguous();
   cache_["perm:" + wname] = pm;
   return pm;
+}
+
+// perm_conv's [k,CP,CP] -> [k,CP/32,CP,32]: the pair kernel's sliced layout
+// (functional.py _conv_weight_sliced), cached under its own key
+torch::Tensor VitsEngine::perm_conv_sliced(const std::string& wname) const {
+  auto it = cache_.find("perms:" + wname);
+  if (it != cache_.end()) return it->second;
+  auto pm = perm_conv(wname);
+  const long k = pm.size(0), CoutP = pm.size(1), CinP = pm.size(2);
+  auto sl = pm.view({k, CoutP, CinP / 32, 32}).permute({0, 2, 1, 3})
+                .contiguous();
+  cache_["perms:" + wname] = sl;
+  return sl;
 }
 
 // [Cin,Cout,k] -> [s,kr,CoutP,CinP] (functional.py _convt_weight_mfma)
@@ -910,17 +929,20 @@ torch::Tensor VitsEngine::generator(torch::Tensor x,
 
   if (gpu() && x.scalar_type() == torch::kBFloat16) {
     // channel-last serving path (vits.py Generator._forward_cl)
+    // int32 lengths for the kernels: converted once per stage (the stage's
+    // transposed conv and all its pairs share it), not once per kernel
     c10::optional<torch::Tensor> lens32;
     auto to32 = [&](const c10::optional<torch::Tensor>& l)
         -> c10::optional<torch::Tensor> {
       if (!l.has_value()) return c10::nullopt;
       return l->to(torch::kInt32).contiguous();
     };
+    lens32 = to32(lens);
     auto xc = x.transpose(1, 2).contiguous();
     xc = conv1d_cl_fused(xc, perm_conv("dec.conv_pre.weight"),
                          bias_f32("dec.conv_pre.bias"),
                          p("dec.conv_pre.weight").size(0), 7, 3, 1, -1.0, 0,
-                         0.0, c10::nullopt, to32(lens));
+                         0.0, c10::nullopt, lens32);
     if (g.has_value() && has("dec.cond.weight")) {
       xc = xc + conv(*g, "dec.cond").transpose(1, 2);
       if (lens.has_value()) {
@@ -932,10 +954,13 @@ torch::Tensor VitsEngine::generator(torch::Tensor x,
     for (long i = 0; i < n_ups; ++i) {
       std::string ui = "dec.ups." + std::to_string(i);
       long s = cfg_.up_rates[i], k = cfg_.up_ks[i];
-      if (lens.has_value()) lens = *lens * s;
+      if (lens.has_value()) {
+        lens = *lens * s;
+        lens32 = to32(lens);
+      }
       xc = convtranspose1d_cl_fused(
           xc, perm_convt(ui + ".weight", s), bias_f32(ui + ".bias"),
-          p(ui + ".weight").size(1), k, s, (k - s) / 2, kLRelu, to32(lens));
+          p(ui + ".weight").size(1), k, s, (k - s) / 2, kLRelu, lens32);
       // fused resblock pairs; the MRF sum and /num_kernels fold into
       // the last pair\'s epilogue (same as the Python path)
       torch::Tensor xs;
@@ -977,7 +1002,7 @@ torch::Tensor VitsEngine::generator(torch::Tensor x,
           xs = resblock_chain_cl_fused(
               out, cache_[key], cache_["chainb:" + rb], kk,
               cfg_.resblock_dil[j][0], cfg_.resblock_dil[j][1],
-              cfg_.resblock_dil[j][2], to32(lens), accum,
+              cfg_.resblock_dil[j][2], lens32, accum,
               last_rb ? 1.0 / (double)n_kernels : 1.0);
           continue;
         }
@@ -988,11 +1013,20 @@ torch::Tensor VitsEngine::generator(torch::Tensor x,
           const bool last = (di == npair - 1);
           c10::optional<torch::Tensor> accum;
           if (last && xs.defined()) accum = xs;
-          out = resblock_pair_cl_fused(
-              out, perm_conv(c1 + ".weight"), bias_f32(c1 + ".bias"),
-              perm_conv(c2 + ".weight"), bias_f32(c2 + ".bias"), kk, d,
-              to32(lens), accum,
-              (last && last_rb) ? 1.0 / (double)n_kernels : 1.0);
+          const double scale =
+              (last && last_rb) ? 1.0 / (double)n_kernels : 1.0;
+          auto w1p = perm_conv(c1 + ".weight");
+          if (w1p.size(1) == w1p.size(2) &&
+              resblock_wlayout_sliced(w1p.size(2)))
+            out = resblock_pair_cl_fused_sliced(
+                out, perm_conv_sliced(c1 + ".weight"), bias_f32(c1 + ".bias"),
+                perm_conv_sliced(c2 + ".weight"), bias_f32(c2 + ".bias"), kk,
+                d, lens32, accum, scale);
+          else
+            out = resblock_pair_cl_fused(
+                out, w1p, bias_f32(c1 + ".bias"),
+                perm_conv(c2 + ".weight"), bias_f32(c2 + ".bias"), kk, d,
+                lens32, accum, scale);
         }
         xs = out;
       }
@@ -1000,7 +1034,7 @@ torch::Tensor VitsEngine::generator(torch::Tensor x,
     }
     xc = conv1d_cl_fused(xc, perm_conv("dec.conv_post.weight"), c10::nullopt,
                          1, 7, 3, 1, kLRelu, 2 /*tanh*/, 0.0, c10::nullopt,
-                         to32(lens));
+                         lens32);
     return xc.transpose(1, 2);
   }
 

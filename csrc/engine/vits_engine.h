@@ -89,6 +89,7 @@ class VitsEngine {
   bool has(const std::string& name) const { return P_.count(name) > 0; }
   c10::optional<torch::Tensor> maybe(const std::string& name) const;
   torch::Tensor perm_conv(const std::string& wname) const;
+  torch::Tensor perm_conv_sliced(const std::string& wname) const;
   torch::Tensor perm_convt(const std::string& wname, long stride) const;
   torch::Tensor bias_f32(const std::string& bname) const;
 

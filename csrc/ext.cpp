@@ -75,6 +75,12 @@ torch::Tensor resblock_pair_cl_fused(torch::Tensor x, torch::Tensor w1_perm,
                                      c10::optional<torch::Tensor> out_lens,
                                      c10::optional<torch::Tensor> accum,
                                      double out_scale);
+bool resblock_wlayout_sliced(long CP);
+torch::Tensor resblock_pair_cl_fused_sliced(
+    torch::Tensor x, torch::Tensor w1_sliced, torch::Tensor b1,
+    torch::Tensor w2_sliced, torch::Tensor b2, long k, long dil,
+    c10::optional<torch::Tensor> out_lens, c10::optional<torch::Tensor> accum,
+    double out_scale);
 torch::Tensor resblock_chain_cl_fused(
     torch::Tensor x, torch::Tensor w_all, torch::Tensor b_all, long k,
     long d1, long d2, long d3, c10::optional<torch::Tensor> out_lens,
@@ -127,6 +133,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "zero-LDS direct channel-last conv (L1/L2-fed MFMA)");
   m.def("resblock_pair_cl_fused", &resblock_pair_cl_fused,
         "fused HiFi-GAN resblock conv pair (xt stays in LDS)");
+  m.def("resblock_wlayout_sliced", &resblock_wlayout_sliced,
+        "does SONATA_RB_WLAYOUT (or the default) select sliced weights at CP");
+  m.def("resblock_pair_cl_fused_sliced", &resblock_pair_cl_fused_sliced,
+        "resblock conv pair, weights in the sliced [k][CP/32][CP][32] layout");
   m.def("resblock_chain_cl_fused", &resblock_chain_cl_fused,
         "whole resblock (3 pairs) fused: intermediates never touch HBM");
   m.def("attn_relpos_cl", &attn_relpos_cl,

@@ -23,14 +23,20 @@
 template <int BN, int WGN, int TC, int XR, int XTR>
 __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
     const bf16* __restrict__ x,    // [B][T][C]
-    const bf16* __restrict__ w1,   // [k][CP][CP] (dilated conv)
+    const bf16* __restrict__ w1,   // [k][CP][CP] (dilated conv) or sliced
     const float* __restrict__ b1,  // [C]
-    const bf16* __restrict__ w2,   // [k][CP][CP] (d=1 conv)
+    const bf16* __restrict__ w2,   // [k][CP][CP] (d=1 conv) or sliced
     const float* __restrict__ b2,  // [C]
     bf16* __restrict__ out,        // [B][T][C]
     const bf16* __restrict__ accum,  // optional: add (xs running sum)
     const int* __restrict__ out_lens,
-    int C, int CP, long T, int k, int dil, float out_scale) {
+    int C, int CP, long T, int k, int dil, float out_scale,
+    int wpitch, int wkstep) {
+  // Weight addressing.  A staging window is (tap, 32-channel K slice c0):
+  // BN rows of 32 ci.  Its first element is tap*CP*CP + c0*wkstep and its
+  // rows are wpitch apart:
+  //   rows   [k][CP][CP]        wpitch = CP, wkstep = 1   (64 B of each row)
+  //   sliced [k][CP/32][CP][32] wpitch = 32, wkstep = CP  (one BN*64 B block)
   constexpr int WGM = 4;
   constexpr int WM = XTR / WGM;
   constexpr int MT = WM / 16;
@@ -55,6 +61,16 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
   }
   const long t0 = (long)tile * BM;
   const int b = blockIdx.z;
+  const long lim = out_lens ? min((long)out_lens[b], T) : T;
+  // Dead tile: every output row lies in the batch padding (t0 >= lim,
+  // uniform over the block, before the first barrier).  Store the zeros
+  // the epilogue would store - rows [t0, min(t0+BM, T)) are one span of
+  // [B][T][C] - and read nothing.
+  if (t0 >= lim) {
+    zero_span_bf16(out + ((long)b * T + t0) * C, (min(t0 + BM, T) - t0) * C,
+                   threadIdx.x, 512);
+    return;
+  }
 
   __shared__ bf16 Xs[XROWS_MAX][BKP];
   __shared__ bf16 Xt[XTR][XTP];
@@ -126,11 +142,12 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
     for (int tap0 = 0; tap0 < k; tap0 += TC) {
       const int ntc = min(TC, k - tap0);
       for (int tc = 0; tc < ntc; ++tc) {
-        const long wbase = ((long)(tap0 + tc) * CP) * CP + c0;
+        const long wbase =
+            ((long)(tap0 + tc) * CP) * CP + (long)c0 * wkstep;
         for (int base = sr_base0; base < BN; base += 128) {
           const int n = base + sr_l;
           *(ulonglong2*)&Ws[tc][n][sr_c] =
-              *(const ulonglong2*)&w1[wbase + (long)n * CP + sr_c];
+              *(const ulonglong2*)&w1[wbase + (long)n * wpitch + sr_c];
         }
       }
       __syncthreads();
@@ -156,7 +173,6 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
   }
 
   // epilogue1 -> LDS xt (bias1 + lrelu; zero outside [0,T) and >= lim)
-  const long lim = out_lens ? min((long)out_lens[b], T) : T;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
 #pragma unroll
@@ -186,11 +202,12 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
     for (int tap0 = 0; tap0 < k; tap0 += TC) {
       const int ntc = min(TC, k - tap0);
       for (int tc = 0; tc < ntc; ++tc) {
-        const long wbase = ((long)(tap0 + tc) * CP) * CP + c0;
+        const long wbase =
+            ((long)(tap0 + tc) * CP) * CP + (long)c0 * wkstep;
         for (int base = sr_base0; base < BN; base += 128) {
           const int n = base + sr_l;
           *(ulonglong2*)&Ws[tc][n][sr_c] =
-              *(const ulonglong2*)&w2[wbase + (long)n * CP + sr_c];
+              *(const ulonglong2*)&w2[wbase + (long)n * wpitch + sr_c];
         }
       }
       __syncthreads();
@@ -738,19 +755,58 @@ torch::Tensor resblock_chain_cl_fused(
   return out;
 }
 
-torch::Tensor resblock_pair_cl_fused(torch::Tensor x, torch::Tensor w1_perm,
-                                     torch::Tensor b1, torch::Tensor w2_perm,
-                                     torch::Tensor b2, long k, long dil,
-                                     c10::optional<torch::Tensor> out_lens,
-                                     c10::optional<torch::Tensor> accum,
-                                     double out_scale) {
+// Which weight layout callers should hand the pair kernel at padded width
+// CP.  SONATA_RB_WLAYOUT=rows|sliced is read on every call (like
+// SONATA_RB_GEOM); unset selects the default.  CP=32 rows are one K slice
+// wide, so its windows are contiguous already and it stays on rows.
+// Default rows: sliced measured neutral overall and 3-5% slower at C=256
+// (KERNELS.md, "Documented experiments").
+#define RB_WLAYOUT_DEFAULT_SLICED false
+bool resblock_wlayout_sliced(long CP) {
+  bool sliced = RB_WLAYOUT_DEFAULT_SLICED;
+  const char* e = getenv("SONATA_RB_WLAYOUT");
+  if (e && e[0]) {
+    TORCH_CHECK(strcmp(e, "rows") == 0 || strcmp(e, "sliced") == 0,
+                "SONATA_RB_WLAYOUT must be rows or sliced, got ", e);
+    sliced = strcmp(e, "sliced") == 0;
+  }
+  return sliced && CP >= 64;
+}
+
+// w_sliced says which weight layout the caller passes (it is never guessed):
+//   false: [k][CP][CP]         (tap, co, ci) - _conv_weight_mfma / perm_conv
+//   true:  [k][CP/32][CP][32]  (tap, K slice, co, ci in slice), CP >= 64 -
+//          every (tap, slice) staging window is one contiguous BN*64 B block
+static torch::Tensor resblock_pair_cl_impl(
+    torch::Tensor x, torch::Tensor w1_perm, torch::Tensor b1,
+    torch::Tensor w2_perm, torch::Tensor b2, long k, long dil,
+    c10::optional<torch::Tensor> out_lens, c10::optional<torch::Tensor> accum,
+    double out_scale, bool w_sliced) {
   TORCH_CHECK(x.dim() == 3 && x.is_cuda() && x.is_contiguous());
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "resblock_cl: bf16 only");
   const long B = x.size(0), T = x.size(1), C = x.size(2);
   TORCH_CHECK(w1_perm.size(0) == k && w2_perm.size(0) == k);
-  const int CP = w1_perm.size(2);
-  TORCH_CHECK(w1_perm.size(1) == CP && w2_perm.size(1) == CP &&
-              w2_perm.size(2) == CP, "resblock_cl: square channel conv");
+  TORCH_CHECK(w1_perm.is_contiguous() && w2_perm.is_contiguous() &&
+              w1_perm.scalar_type() == at::kBFloat16 &&
+              w2_perm.scalar_type() == at::kBFloat16,
+              "resblock_cl: weights must be contiguous bf16");
+  TORCH_CHECK(w1_perm.sizes() == w2_perm.sizes(),
+              "resblock_cl: w1 and w2 must have one shape");
+  int CP;
+  if (w_sliced) {
+    TORCH_CHECK(w1_perm.dim() == 4 && w1_perm.size(3) == BK,
+                "resblock_cl: sliced weights are [k][CP/32][CP][32]");
+    CP = w1_perm.size(2);
+    TORCH_CHECK(CP >= 64 && w1_perm.size(1) * BK == CP,
+                "resblock_cl: sliced weights are [k][CP/32][CP][32], CP >= 64");
+  } else {
+    TORCH_CHECK(w1_perm.dim() == 3, "resblock_cl: weights are [k][CP][CP]");
+    CP = w1_perm.size(2);
+    TORCH_CHECK(w1_perm.size(1) == CP, "resblock_cl: square channel conv");
+  }
+  TORCH_CHECK(C <= CP, "resblock_cl: x has more channels than the weights");
+  const int wpitch = w_sliced ? BK : CP;
+  const int wkstep = w_sliced ? CP : 1;
   TORCH_CHECK((k - 1) * dil <= 52, "resblock_cl: halo too large");
   auto out = torch::empty_like(x);
   if (out.numel() == 0) return out;
@@ -787,7 +843,7 @@ torch::Tensor resblock_pair_cl_fused(torch::Tensor x, torch::Tensor w1_perm,
     n_cu = prop.multiProcessorCount;
   }
   const bool persist_ok =
-      persist_on && ((CP == 32) || (CP == 64 && k == 3));
+      persist_on && !w_sliced && ((CP == 32) || (CP == 64 && k == 3));
   if (persist_ok) {
     const int BMp = 256 - (int)(k - 1);
     const int tiles_per_b = (int)((T + BMp - 1) / BMp);
@@ -839,7 +895,7 @@ torch::Tensor resblock_pair_cl_fused(torch::Tensor x, torch::Tensor w1_perm,
                      (const bf16*)w2_perm.data_ptr(),                       \
                      b2f.data_ptr<float>(), (bf16*)out.data_ptr(), accum_p, \
                      lens_p, (int)C, CP, T, (int)k, (int)dil,               \
-                     (float)out_scale)
+                     (float)out_scale, wpitch, wkstep)
   // XR bucket = 128 + (k-1)*dil rounded up; TC=3 covers k=3 in one
   // chunk and k=7/11 in 3/4 chunks (fewer barrier pairs); C=256 keeps
   // TC=2 for LDS.
@@ -876,4 +932,24 @@ torch::Tensor resblock_pair_cl_fused(torch::Tensor x, torch::Tensor w1_perm,
 #undef RB_XR64
 #undef LAUNCH_RB
   return out;
+}
+
+torch::Tensor resblock_pair_cl_fused(torch::Tensor x, torch::Tensor w1_perm,
+                                     torch::Tensor b1, torch::Tensor w2_perm,
+                                     torch::Tensor b2, long k, long dil,
+                                     c10::optional<torch::Tensor> out_lens,
+                                     c10::optional<torch::Tensor> accum,
+                                     double out_scale) {
+  return resblock_pair_cl_impl(x, w1_perm, b1, w2_perm, b2, k, dil, out_lens,
+                               accum, out_scale, false);
+}
+
+// Second entry point for the sliced weight layout [k][CP/32][CP][32].
+torch::Tensor resblock_pair_cl_fused_sliced(
+    torch::Tensor x, torch::Tensor w1_sliced, torch::Tensor b1,
+    torch::Tensor w2_sliced, torch::Tensor b2, long k, long dil,
+    c10::optional<torch::Tensor> out_lens, c10::optional<torch::Tensor> accum,
+    double out_scale) {
+  return resblock_pair_cl_impl(x, w1_sliced, b1, w2_sliced, b2, k, dil,
+                               out_lens, accum, out_scale, true);
 }

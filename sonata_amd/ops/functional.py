@@ -147,6 +147,26 @@ def _conv_weight_mfma(weight: torch.Tensor) -> torch.Tensor:
     return perm
 
 
+def _slice_weight_windows(perm: torch.Tensor) -> torch.Tensor:
+    """[k, CoutP, CinP] -> [k, CinP/32, CoutP, 32]: the same numbers, stored
+    so that each (tap, 32-channel K slice) window the resblock pair kernel
+    stages is one contiguous block.  Element (tap, co, ci) moves to
+    (tap, ci // 32, co, ci % 32)."""
+    k, CoutP, CinP = perm.shape
+    return perm.view(k, CoutP, CinP // 32, 32).permute(0, 2, 1, 3).contiguous()
+
+
+def _conv_weight_sliced(weight: torch.Tensor) -> torch.Tensor:
+    """Cache the sliced layout next to the `_conv_weight_mfma` one: built
+    once per weight, never per call."""
+    cached = getattr(weight, "_sonata_perm_sliced", None)
+    if cached is not None:
+        return cached
+    sliced = _slice_weight_windows(_conv_weight_mfma(weight))
+    weight._sonata_perm_sliced = sliced
+    return sliced
+
+
 def _convt_weight_mfma(weight: torch.Tensor, stride: int) -> torch.Tensor:
     """ConvTranspose1d weight [Cin,Cout,k] -> phase layout
     [s, kr_max, CoutP, CinP] bf16 where phase r tap m holds W[:, :, r+s*m]."""
@@ -402,7 +422,13 @@ def resblock_pair_cl(
                  and w1p.shape[1] in (32, 64, 128, 256))
     if fused:
         ext = hip_ext(required=True)
-        return ext.resblock_pair_cl_fused(
+        # SONATA_RB_WLAYOUT=rows|sliced, read by the extension per call
+        if ext.resblock_wlayout_sliced(w1p.shape[1]):
+            op = ext.resblock_pair_cl_fused_sliced
+            w1p, w2p = _conv_weight_sliced(w1), _conv_weight_sliced(w2)
+        else:
+            op = ext.resblock_pair_cl_fused
+        return op(
             x.contiguous(), w1p, _bias_f32(b1), w2p, _bias_f32(b2),
             k, dilation,
             _lens_i32(out_lens, x.device),
