@@ -101,6 +101,21 @@ std::vector<torch::Tensor> wsola_rows(torch::Tensor x, torch::Tensor in_len,
 std::vector<torch::Tensor> pcm16_rows(torch::Tensor x, torch::Tensor len,
                                       long N_out, bool peak_normalize);
 long pcm_tile();
+// stream.hip
+torch::Tensor gather_windows(std::vector<torch::Tensor> zs,
+                             std::vector<int64_t> src,
+                             std::vector<int64_t> row,
+                             std::vector<int64_t> start,
+                             std::vector<int64_t> length, long l_max);
+torch::Tensor stream_seam_rows(torch::Tensor wav, std::vector<int64_t> lo,
+                               std::vector<int64_t> hi,
+                               std::vector<int64_t> ext,
+                               std::vector<int64_t> prev_ext,
+                               std::vector<int64_t> slot,
+                               torch::Tensor tails_in,
+                               torch::Tensor tails_out, torch::Tensor ramp,
+                               long n_out);
+long seam_crossfade_samples();
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "sonata_amd hand-written CDNA4 (gfx950) kernels";
@@ -158,6 +173,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("len"), py::arg("n_out"),
         py::arg("peak_normalize") = true);
   m.attr("PCM_TILE") = pcm_tile();
+  m.def("gather_windows", &gather_windows,
+        "pack ragged latent windows of several [b,C,F] sources into "
+        "[R,C,l_max], zero padded; one launch",
+        py::arg("zs"), py::arg("src"), py::arg("row"), py::arg("start"),
+        py::arg("length"), py::arg("l_max"));
+  m.def("stream_seam_rows", &stream_seam_rows,
+        "per-row trim + 42-sample crossfade of decoded stream chunks; "
+        "writes tails_out at the named slots, returns out [R,n_out] f32",
+        py::arg("wav"), py::arg("lo"), py::arg("hi"), py::arg("ext"),
+        py::arg("prev_ext"), py::arg("slot"), py::arg("tails_in"),
+        py::arg("tails_out"), py::arg("ramp"), py::arg("n_out"));
+  m.attr("SEAM_CROSSFADE") = seam_crossfade_samples();
 
   // C++ inference runtime (csrc/engine): the ort-replacement executor.
   py::class_<sonata::VitsEngine>(m, "VitsEngine")

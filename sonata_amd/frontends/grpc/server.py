@@ -28,7 +28,7 @@ from typing import Dict, Optional
 import grpc
 
 from ...core import SonataError
-from ...synth.batcher import DynamicBatcher
+from ...synth.batcher import DynamicBatcher, StreamBatcher
 from ...synth.synthesizer import AudioOutputConfig, SonataSpeechSynthesizer
 from .proto import (MESSAGES, MODE_LAZY, QUALITY_VALUES, RPCS, SERVICE_NAME)
 
@@ -56,6 +56,16 @@ class _Voice:
         # dynamic batcher: concurrent RPCs coalesce into padded GPU
         # batches (per-utterance seeding makes batching invisible)
         self.batcher = DynamicBatcher(synth.model)
+        # SONATA_STREAM_BATCH=1 (opt-in): concurrent realtime streams on
+        # this voice share chunk decodes through a StreamBatcher
+        if (os.environ.get("SONATA_STREAM_BATCH", "0") == "1"
+                and hasattr(synth.model, "stream_round")):
+            synth.stream_batcher = StreamBatcher(synth.model)
+
+    def close(self) -> None:
+        self.batcher.close()
+        if self.synth.stream_batcher is not None:
+            self.synth.stream_batcher.close()
 
 
 class SonataGrpcService:
@@ -158,7 +168,7 @@ class SonataGrpcService:
         if winner is not v:
             # concurrent LoadVoice for the same config: release the
             # loser's batcher worker thread and let its weights be GC'd
-            v.batcher.close()
+            v.close()
             v = winner
         log.info("loaded voice %s from %s on %s", voice_id,
                  request.config_path, self.device)

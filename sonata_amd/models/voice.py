@@ -76,6 +76,12 @@ class VitsVoice(SonataModel):
         # Cross-voice concurrency is unaffected; the gRPC batcher
         # already funnels per-voice work through one thread.
         self._infer_lock = threading.Lock()
+        # batched streams (stream_open / stream_round): one kept crossfade
+        # tail per live stream, [S, CROSSFADE_SAMPLES] f32 on the device
+        self._tail_lock = threading.Lock()
+        self._tail_free: List[int] = []
+        self._tails: Optional[torch.Tensor] = None
+        self._ramp: Optional[torch.Tensor] = None
         self._tashkeel = None
         if config.espeak_voice.startswith("ar"):
             from ..text.tashkeel import TashkeelModel
@@ -487,6 +493,288 @@ class VitsVoice(SonataModel):
             self._pin_events[pwhich].synchronize()
             wav = self._pin_bufs[pwhich][:pn].numpy().copy()
             yield trim_and_emit(pspec, wav)
+
+    # ------------------------------------------------------------------ #
+    # batched streams: many realtime streams share one chunk decode
+    # ------------------------------------------------------------------ #
+    @torch.no_grad()
+    def stream_open(self, phonemes_batch: Sequence[str], chunk_size=45,
+                    chunk_padding: int = 3) -> List["StreamState"]:
+        """Encode a list of sentences in ONE batched encoder call and return
+        one StreamState per sentence, to be advanced by stream_round.
+        `chunk_size` is an int or one int per sentence.  Speaker and scales
+        are those of the current synthesis config; seeds are per utterance,
+        as in stream_synthesis.  Holds the inference lock for this call
+        only.  Release unfinished states with stream_close."""
+        B = len(phonemes_batch)
+        if isinstance(chunk_size, int):
+            chunk_size = [chunk_size] * B
+        chunk_size = [int(c) for c in chunk_size]
+        assert len(chunk_size) == B, "one chunk_size per sentence"
+        if B == 0:
+            return []
+        cfg = self.get_synthesis_config()
+        id_lists = [self._encode_ids(p) for p in phonemes_batch]
+        T = max(len(i) for i in id_lists)
+        ids = torch.zeros((B, T), dtype=torch.long)
+        lengths = torch.zeros((B,), dtype=torch.long)
+        for b, il in enumerate(id_lists):
+            ids[b, : len(il)] = torch.tensor(il, dtype=torch.long)
+            lengths[b] = len(il)
+        ids = ids.to(self.device)
+        lengths = lengths.to(self.device)
+        sid = self._sid_tensor(B, cfg.speaker_id)
+        with self._infer_lock:
+            with stage_timer("encode", self.device):
+                if self._engine is not None:
+                    z, y_mask, g = self._engine.infer_encoder(
+                        ids, lengths, sid, cfg.noise_scale, cfg.length_scale,
+                        cfg.noise_w,
+                        [_utterance_seed(p, cfg.speaker_id)
+                         for p in phonemes_batch])
+                    if g is not None and (not g.numel()):
+                        g = None
+                else:
+                    z, y_mask, g = self.net.infer_encoder(
+                        ids, lengths, sid=sid, noise_scale=cfg.noise_scale,
+                        length_scale=cfg.length_scale, noise_w=cfg.noise_w,
+                        generators=self._generators(phonemes_batch,
+                                                    cfg.speaker_id))
+                # one host sync: every row's frame count
+                frames = (y_mask[:, 0, :] > 0).sum(-1).tolist()
+            slots = self._tail_slots_take(B)
+        return [
+            StreamState(
+                index=b, z=z, row=b, frames=int(frames[b]),
+                g=g[b : b + 1] if g is not None else None,
+                plan=chunk_plan(int(frames[b]), chunk_size[b], chunk_padding),
+                slot=slots[b])
+            for b in range(B)]
+
+    def stream_close(self, states) -> None:
+        """Release the tail slots of states that will not be advanced any
+        further (finished states have released theirs already)."""
+        with self._tail_lock:
+            for s in states:
+                if s.slot is not None:
+                    self._tail_free.append(s.slot)
+                    s.slot = None
+                s.done = True
+
+    def _tail_slots_take(self, n: int) -> List[int]:
+        """n free tail slots; grows the device buffer when they run out
+        (called under _infer_lock: rounds see either buffer whole)."""
+        from ..audio.samples import _quarter_sine_ramp
+
+        with self._tail_lock:
+            if self._ramp is None:
+                self._ramp = torch.from_numpy(
+                    _quarter_sine_ramp(CROSSFADE_SAMPLES).copy()
+                ).to(self.device)
+            have = 0 if self._tails is None else self._tails.shape[0]
+            if len(self._tail_free) < n:
+                grow = max(64, n - len(self._tail_free), have)
+                tails = torch.zeros((have + grow, CROSSFADE_SAMPLES),
+                                    dtype=torch.float32, device=self.device)
+                if have:
+                    tails[:have].copy_(self._tails)
+                self._tails = tails
+                self._tail_free.extend(range(have + grow - 1, have - 1, -1))
+            return [self._tail_free.pop() for _ in range(n)]
+
+    @torch.no_grad()
+    def _round_enqueue(self, states, pcm: bool, pins=None):
+        """Take each live state's next chunk and enqueue gather -> decode ->
+        seam (-> pcm) and the copy of the packed rows to the host.  Caller
+        holds _infer_lock.  Returns what _round_collect needs, or None when
+        no state is live."""
+        from ..ops import gather_windows, pcm16_rows, stream_seam_rows
+
+        live = [s for s in states if not s.done]
+        if not live:
+            return None
+        hop = self.net.arch.hop_length
+        specs = [s.take_spec() for s in live]
+        length = [sp.mel_end - sp.mel_start for sp in specs]
+        l_max = max(length)
+        zs: list = []
+        src = []
+        for s in live:
+            for i, z in enumerate(zs):
+                if z is s.z:
+                    src.append(i)
+                    break
+            else:
+                src.append(len(zs))
+                zs.append(s.z)
+        with stage_timer("decode_round", self.device):
+            z_c = gather_windows(zs, src, [s.row for s in live],
+                                 [sp.mel_start for sp in specs], length,
+                                 l_max)
+            g = None
+            if live[0].g is not None:
+                g = (live[0].g if len(live) == 1
+                     else torch.cat([s.g for s in live], dim=0))
+            wav = self._decode_windows(z_c, length, g)
+            lo = [sp.trim_left_frames * hop for sp in specs]
+            hi = [n * hop - sp.trim_right_frames * hop
+                  for n, sp in zip(length, specs)]
+            ext = [0 if sp.is_last else min(CROSSFADE_SAMPLES,
+                                            sp.trim_right_frames * hop)
+                   for sp in specs]
+            out, out_len, _ = stream_seam_rows(
+                wav, lo, hi, ext, [s.prev_ext for s in live],
+                [s.slot for s in live], self._tails, self._ramp,
+                tails_out=self._tails)
+            if pcm:
+                out, _ = pcm16_rows(out, out_len)
+        finished = []
+        for s, sp, e in zip(live, specs, ext):
+            s.prev_ext = e
+            if sp.is_last:
+                finished.append(s)
+        if finished:
+            self.stream_close(finished)
+        event = None
+        if self.device.type == "cuda":
+            host = (pins if pins is not None else self._round_pins()).take(
+                out.shape, out.dtype)
+            host.copy_(out, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record()
+        else:
+            host = out
+        return live, out_len.tolist(), host, event
+
+    def _decode_windows(self, z_c, length, g):
+        """Eager ragged decode of packed windows [R, C, l_max] with
+        `length[r]` valid frames each -> [R, 1, l_max * hop]."""
+        lens_t = torch.tensor(length, dtype=torch.long, device=self.device)
+        # inside its valid frames a stream's y_mask is 1
+        m_c = (torch.arange(z_c.shape[-1], device=self.device)[None, :]
+               < lens_t[:, None]).to(z_c.dtype).unsqueeze(1)
+        if self._engine is not None:
+            return self._engine.decode(z_c, m_c, g, lens_t)
+        return self.net.decode(z_c, m_c, g, lengths=lens_t)
+
+    def _round_pins(self):
+        if not hasattr(self, "_round_pin_bufs"):
+            self._round_pin_bufs = _PinnedPair()
+        return self._round_pin_bufs
+
+    @staticmethod
+    def _round_collect(pending):
+        """Wait for a round's host copy and slice it per stream."""
+        live, out_len, host, event = pending
+        if event is not None:
+            event.synchronize()
+        rows = host.numpy()
+        return [(s, rows[r, : out_len[r]].copy())
+                for r, s in enumerate(live)]
+
+    def stream_round(self, states, pcm: bool = False):
+        """Advance every live state by one chunk in ONE decode: gather the
+        latent windows, decode them as a ragged batch, trim and crossfade
+        per stream on the device, copy the packed rows to the host once.
+        Returns [(state, chunk)] for the states that were live: float32
+        chunks, or int16 (ops.pcm16_rows of the float chunk) with pcm=True.
+        A state whose chunk was its last is finished (state.done).  Holds
+        the inference lock for the round only, and always decodes eagerly
+        (R and the window length change from round to round)."""
+        with self._infer_lock:
+            pending = self._round_enqueue(states, pcm)
+            if pending is None:
+                return []
+            # collected under the lock: the pinned pair belongs to the voice
+            return self._round_collect(pending)
+
+    def stream_synthesis_batch(self, phonemes_batch: Sequence[str],
+                               chunk_size=45, chunk_padding: int = 3,
+                               pcm: bool = False):
+        """stream_synthesis for a list of sentences at once: yields (index,
+        chunk) with, per index, the chunk boundaries, total length and seams
+        of stream_synthesis.  One encoder call, then one decode per round
+        for all streams still running.  On cuda round r+1 is enqueued before
+        round r's host copy is consumed (the first round is emitted first).
+        The inference lock is held per call and per round, never across a
+        yield; closing the iterator releases the streams' slots."""
+        states = self.stream_open(phonemes_batch, chunk_size, chunk_padding)
+        pins = _PinnedPair() if self.device.type == "cuda" else None
+        try:
+            with self._infer_lock:
+                pending = self._round_enqueue(states, pcm, pins)
+            pipelined = self.device.type == "cuda"
+            first = True
+            while pending is not None:
+                ahead = pipelined and not first
+                nxt = None
+                if ahead:
+                    with self._infer_lock:
+                        nxt = self._round_enqueue(states, pcm, pins)
+                for s, chunk in self._round_collect(pending):
+                    yield s.index, chunk
+                if not ahead:
+                    with self._infer_lock:
+                        nxt = self._round_enqueue(states, pcm, pins)
+                first = False
+                pending = nxt
+        finally:
+            self.stream_close(states)
+
+
+class StreamState:
+    """One stream of VitsVoice.stream_open: its latent tensor and row, frame
+    count, conditioning row, chunk plan, tail slot and the crossfade length
+    its previous chunk left."""
+
+    __slots__ = ("index", "z", "row", "frames", "g", "slot", "prev_ext",
+                 "done", "_plan", "_next")
+
+    def __init__(self, index, z, row, frames, g, plan, slot):
+        self.index = index
+        self.z = z
+        self.row = row
+        self.frames = frames
+        self.g = g
+        self.slot = slot
+        self.prev_ext = 0
+        self.done = False
+        self._plan = plan
+        self._next = next(plan, None)
+        if self._next is None:
+            self.done = True
+
+    @property
+    def next_spec(self):
+        """The ChunkSpec the next round decodes (None when finished)."""
+        return None if self.done else self._next
+
+    def take_spec(self):
+        spec = self._next
+        self._next = None if spec.is_last else next(self._plan, None)
+        return spec
+
+
+class _PinnedPair:
+    """Two pinned host buffers handed out in turn, grown on demand: a round's
+    rows stay valid while the next round is enqueued."""
+
+    def __init__(self):
+        self._bufs = [None, None]
+        self._which = 0
+
+    def take(self, shape, dtype) -> torch.Tensor:
+        n = 1
+        for d in shape:
+            n *= int(d)
+        nbytes = n * torch.empty((), dtype=dtype).element_size()
+        buf = self._bufs[self._which]
+        if buf is None or buf.shape[0] < nbytes:
+            buf = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8,
+                              pin_memory=True)
+            self._bufs[self._which] = buf
+        self._which ^= 1
+        return buf[:nbytes].view(dtype).view(*shape)
 
 
 # --------------------------------------------------------------------------- #

@@ -75,4 +75,6 @@ from .functional import (  # noqa: F401,E402
     wsola_rows,
     apply_prosody_rows,
     pcm16_rows,
+    gather_windows,
+    stream_seam_rows,
 )

@@ -846,3 +846,119 @@ def pcm16_rows(x: torch.Tensor, lengths, silence=None,
     pcm, _peaks = ext.pcm16_rows(x, _i32(lens, x.device), n_out,
                                  bool(peak_normalize))
     return pcm, out_lengths
+
+
+# --------------------------------------------------------------------------- #
+# batched realtime streams (csrc/stream.hip): pack ragged latent windows into
+# one decode batch, and trim / crossfade the decoded rows per stream.  Pure
+# data movement plus one rounded multiply-add per seam sample: the CPU paths
+# (slicing, audio.samples.crossfade) are the oracle and the kernels match
+# them bit for bit.
+# --------------------------------------------------------------------------- #
+SEAM_CROSSFADE = 42  # samples of one kept tail (csrc/stream.hip SEAM_XF)
+
+
+def gather_windows(zs, src, row, start, length, l_max: int) -> torch.Tensor:
+    """Pack windows of several latent tensors into one decode batch.
+    `zs`: list of [b_i, C, F_i] tensors (one dtype, one C; separate
+    allocations are fine).  Output row r is zs[src[r]][row[r], :, start[r] :
+    start[r] + length[r]] followed by zeros up to `l_max`: [R, C, l_max].
+    The matching mask is t < length[r].  One launch on the GPU."""
+    zs = list(zs)
+    assert zs, "no source tensors"
+    R = len(src)
+    src, row, start, length = (_per_row_int(v, R)
+                               for v in (src, row, start, length))
+    l_max = int(l_max)
+    z0 = zs[0]
+    C = z0.shape[1]
+    for z in zs:
+        assert z.dim() == 3 and z.shape[1] == C and z.dtype == z0.dtype, \
+            "sources differ in dtype or C"
+    for r in range(R):
+        assert 0 <= src[r] < len(zs), "src out of range"
+        z = zs[src[r]]
+        assert 0 <= row[r] < z.shape[0], "row out of range"
+        assert (start[r] >= 0 and 0 <= length[r] <= l_max
+                and start[r] + length[r] <= z.shape[2]), \
+            "window outside its source row"
+    if not use_hip(z0):
+        out = torch.zeros((R, C, l_max), dtype=z0.dtype, device=z0.device)
+        for r in range(R):
+            out[r, :, : length[r]] = zs[src[r]][
+                row[r], :, start[r] : start[r] + length[r]]
+        return out
+    ext = hip_ext(required=True)
+    zs = [z if (z.shape[2] <= 1 or z.stride(2) == 1) else z.contiguous()
+          for z in zs]
+    return ext.gather_windows(zs, src, row, start, length, l_max)
+
+
+def stream_seam_rows(wav: torch.Tensor, lo, hi, ext, prev_ext, slot,
+                     tails_in: torch.Tensor, ramp: torch.Tensor,
+                     tails_out: Optional[torch.Tensor] = None):
+    """Trim and crossfade R decoded stream chunks at once (the per-stream
+    trim_and_emit of VitsVoice._stream_decode).  `wav` [R, 1, N] (or [R, N])
+    is the decoder output in its dtype, widened to f32 as .float() does.
+    Per row: cur = wav[r, lo : hi + ext]; if prev_ext > 0 its first prev_ext
+    samples become tail[j] * ramp[n-1-j] + cur[j] * ramp[j] with tail =
+    tails_in[slot[r]], n = prev_ext; out[r] = cur[: len(cur) - ext] and
+    tails_out[slot[r]] = cur[len(cur) - ext :].  `ramp` is
+    audio.samples._quarter_sine_ramp(SEAM_CROSSFADE) on wav's device.
+    Returns (out f32 [R, n_out], out_len [R], tails_out): n_out is the longest
+    row rounded up to a multiple of 8 (ops.pcm16_rows takes out and out_len as
+    they are), columns past out_len[r] are 0, and slots not named keep their
+    contents.  `tails_out` defaults to a copy of tails_in; passing tails_in
+    itself updates it in place (a row's old tail is read before its new one
+    is written)."""
+    if wav.dim() == 3:
+        assert wav.shape[1] == 1, "wav must be [R, 1, N]"
+        wav = wav[:, 0, :]
+    R, N = wav.shape
+    lo, hi, ex, pe, slot = (_per_row_int(v, R)
+                            for v in (lo, hi, ext, prev_ext, slot))
+    S = tails_in.shape[0]
+    assert tails_in.shape == (S, SEAM_CROSSFADE) \
+        and tails_in.dtype == torch.float32, "tails must be f32 [S, 42]"
+    assert ramp.shape == (SEAM_CROSSFADE,) and ramp.dtype == torch.float32
+    for r in range(R):
+        assert pe[r] in (0, SEAM_CROSSFADE), "prev_ext must be 0 or 42"
+        assert ex[r] in (0, SEAM_CROSSFADE), "ext must be 0 or 42"
+        assert 0 <= lo[r] <= hi[r] and hi[r] + ex[r] <= N, \
+            "[lo, hi + ext) outside the row"
+        assert hi[r] - lo[r] >= pe[r], "chunk shorter than its seam"
+        assert 0 <= slot[r] < S, "slot out of range"
+    assert len(set(slot)) == R, "rows must name distinct slots"
+    out_len = [h - l for l, h in zip(lo, hi)]
+    n_out = _round_up(max(out_len, default=0), 8)
+    out_lengths = torch.tensor(out_len, dtype=torch.long)
+    if tails_out is None:
+        tails_out = tails_in.clone()
+    assert tails_out.shape == tails_in.shape \
+        and tails_out.dtype == torch.float32
+    if not use_hip(wav):
+        import numpy as np
+
+        from ..audio.samples import crossfade
+
+        wn = wav.detach().float().cpu().numpy()
+        tin = tails_in.detach().cpu().numpy()
+        out = np.zeros((R, n_out), dtype=np.float32)
+        new_tails = {}
+        for r in range(R):
+            cur = wn[r, lo[r] : hi[r] + ex[r]]
+            if pe[r]:
+                cur = crossfade(tin[slot[r]], cur, pe[r])
+            out[r, : out_len[r]] = cur[: out_len[r]]
+            if ex[r]:
+                new_tails[slot[r]] = cur[out_len[r] :].copy()
+        for s, t in new_tails.items():
+            tails_out[s] = torch.from_numpy(t).to(tails_out.device)
+        return torch.from_numpy(out).to(wav.device), out_lengths, tails_out
+    hext = hip_ext(required=True)
+    assert hext.SEAM_CROSSFADE == SEAM_CROSSFADE
+    if N > 1 and wav.stride(1) != 1:
+        wav = wav.contiguous()
+    out = hext.stream_seam_rows(wav, lo, hi, ex, pe, slot, tails_in,
+                                tails_out, ramp, n_out)
+    return out, out_lengths, tails_out

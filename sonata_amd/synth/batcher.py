@@ -125,3 +125,209 @@ class DynamicBatcher:
         sil = (silence_samples(silence_ms, audio.info.sample_rate)
                if silence_ms else 0)
         return PcmAudio.from_audio(audio, sil)
+
+
+class _StreamHandle:
+    """One stream of a StreamBatcher: its request, its chunk queue and,
+    once opened, its model state."""
+
+    __slots__ = ("phonemes", "chunk_size", "chunk_padding", "pcm", "q",
+                 "cancelled", "state")
+
+    def __init__(self, phonemes, chunk_size, chunk_padding, pcm):
+        self.phonemes = phonemes
+        self.chunk_size = int(chunk_size)
+        self.chunk_padding = int(chunk_padding)
+        self.pcm = bool(pcm)
+        self.q: "queue.Queue" = queue.Queue()
+        self.cancelled = False
+        self.state = None
+
+    def window(self) -> int:
+        spec = self.state.next_spec
+        return spec.mel_end - spec.mel_start
+
+
+class _StreamIter:
+    """Iterator over one stream's chunks.  close() (or dropping the
+    iterator) takes the stream out of the batcher at its next tick."""
+
+    _DONE = object()
+
+    def __init__(self, handle: _StreamHandle):
+        self._h = handle
+        self._ended = False
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._ended:
+            raise StopIteration
+        item = self._h.q.get()
+        if item is self._DONE:
+            self._ended = True
+            raise StopIteration
+        if isinstance(item, BaseException):
+            self._ended = True
+            raise item
+        return item
+
+    def close(self) -> None:
+        self._ended = True
+        self._h.cancelled = True
+
+    def __del__(self):
+        if not self._ended:
+            self._h.cancelled = True
+
+
+class StreamBatcher:
+    """Coalesce concurrent realtime streams on one voice into shared chunk
+    decodes: the streaming counterpart of DynamicBatcher.
+
+    `open` queues a sentence and returns the iterator of its chunks.  One
+    worker owns the live streams.  Each tick it admits what is queued
+    (waiting `max_wait_ms` for company only when nothing is live), opens the
+    newcomers in ONE model.stream_open (one batched encoder call), and
+    advances every live stream by one chunk with model.stream_round: one
+    decode per bucket of similar window length.  Streams join and leave
+    between ticks; per-utterance seeding keeps each stream's audio
+    independent of what it shares a round with."""
+
+    def __init__(self, model: SonataModel, max_streams: int = 64,
+                 max_wait_ms: float = 2.0):
+        self.model = model
+        self.max_streams = max_streams
+        self.max_wait = max_wait_ms / 1000.0
+        self._q: "queue.Queue[Optional[_StreamHandle]]" = queue.Queue()
+        self._closed = False
+        self._worker = threading.Thread(target=self._run, daemon=True,
+                                        name="sonata_stream_batcher")
+        self._worker.start()
+
+    def open(self, phonemes: str, chunk_size: int = 45,
+             chunk_padding: int = 3, pcm: bool = False):
+        """Start one stream; returns the iterator of its chunks (float32
+        arrays, or int16 with pcm=True), those model.stream_synthesis
+        yields for the same arguments."""
+        if self._closed:
+            raise RuntimeError("stream batcher closed")
+        h = _StreamHandle(phonemes, chunk_size, chunk_padding, pcm)
+        self._q.put(h)
+        return _StreamIter(h)
+
+    def close(self) -> None:
+        """End the worker; streams still running end with an error."""
+        self._closed = True
+        self._q.put(None)
+        self._worker.join(timeout=10)
+
+    # ------------------------------------------------------------------ #
+    def _admit(self, n_live: int):
+        """Handles to open this tick, and whether close() was seen."""
+        room = self.max_streams - n_live
+        new: List[_StreamHandle] = []
+        if room <= 0:
+            return new, False
+        if n_live == 0:
+            first = self._q.get()  # idle: sleep until somebody arrives
+            if first is None:
+                return new, True
+            new.append(first)
+        wait = self.max_wait if n_live == 0 else 0.0
+        while len(new) < room:
+            try:
+                nxt = self._q.get(timeout=wait) if wait else \
+                    self._q.get_nowait()
+            except queue.Empty:
+                break
+            if nxt is None:
+                return new, True
+            new.append(nxt)
+            wait = 0.0  # after the first wait, drain non-blocking
+        return new, False
+
+    def _fail(self, handles, exc: BaseException) -> None:
+        states = [h.state for h in handles if h.state is not None]
+        if states:
+            try:
+                self.model.stream_close(states)
+            except Exception:  # noqa: BLE001 - the first error is the news
+                pass
+        for h in handles:
+            h.q.put(exc)
+
+    def _open(self, new: List[_StreamHandle]) -> List[_StreamHandle]:
+        new = [h for h in new if not h.cancelled]
+        opened: List[_StreamHandle] = []
+        # one stream_open per chunk_padding (in practice: one)
+        for pad in sorted({h.chunk_padding for h in new}):
+            group = [h for h in new if h.chunk_padding == pad]
+            try:
+                states = self.model.stream_open(
+                    [h.phonemes for h in group],
+                    [h.chunk_size for h in group], pad)
+            except BaseException as e:  # noqa: BLE001 - reaches the callers
+                self._fail(group, e)
+                continue
+            for h, s in zip(group, states):
+                h.state = s
+            opened.extend(group)
+        return opened
+
+    @staticmethod
+    def _buckets(live: List[_StreamHandle]) -> List[List[_StreamHandle]]:
+        """Shortest windows first, cut where the next window is more than
+        twice the bucket's shortest (DynamicBatcher._flush's rule on window
+        length): a newcomer's 45-frame chunk neither pays for nor waits
+        behind a 225-frame one.  Float and PCM streams decode apart."""
+        out = []
+        for pcm in (False, True):
+            part = sorted((h for h in live if h.pcm == pcm),
+                          key=_StreamHandle.window)
+            start = 0
+            for i in range(1, len(part) + 1):
+                if i == len(part) or (
+                        part[i].window() > 2 * max(part[start].window(), 8)):
+                    out.append(part[start:i])
+                    start = i
+        out.sort(key=lambda b: b[0].window())
+        return out
+
+    def _round(self, bucket: List[_StreamHandle]) -> List[_StreamHandle]:
+        """One decode for the bucket; returns the handles still live."""
+        try:
+            chunks = self.model.stream_round([h.state for h in bucket],
+                                             pcm=bucket[0].pcm)
+        except BaseException as e:  # noqa: BLE001 - reaches the callers
+            self._fail(bucket, e)
+            return []
+        by_state = {id(h.state): h for h in bucket}
+        for state, chunk in chunks:
+            by_state[id(state)].q.put(chunk)
+        still = []
+        for h in bucket:
+            if h.state.done:
+                h.q.put(_StreamIter._DONE)
+            else:
+                still.append(h)
+        return still
+
+    def _run(self) -> None:
+        live: List[_StreamHandle] = []
+        while True:
+            new, closing = self._admit(len(live))
+            if new:
+                live.extend(self._open(new))
+            gone = [h for h in live if h.cancelled]
+            if gone:
+                self.model.stream_close([h.state for h in gone])
+                live = [h for h in live if not h.cancelled]
+            if closing:
+                self._fail(live, RuntimeError("stream batcher closed"))
+                return
+            nxt: List[_StreamHandle] = []
+            for bucket in self._buckets(live):
+                nxt.extend(self._round(bucket))
+            live = nxt

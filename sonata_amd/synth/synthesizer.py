@@ -114,6 +114,10 @@ class SonataSpeechSynthesizer:
 
     def __init__(self, model: SonataModel):
         self.model = model
+        # optional synth.batcher.StreamBatcher on the same model: when set,
+        # synthesize_streamed opens its sentences through it, so concurrent
+        # realtime streams share chunk decodes
+        self.stream_batcher = None
 
     # ------------------------------------------------------------------ #
     def audio_output_info(self) -> AudioInfo:
@@ -250,7 +254,10 @@ class SonataSpeechSynthesizer:
                     # (faster) chunks; the in-sentence chunker grows
                     # further.  The 1024 cap matches MAX_CHUNK_SIZE.
                     cs = min(chunk_size * (n_done + 1), 1024)
-                    if self.model.supports_streaming_output:
+                    if (self.stream_batcher is not None
+                            and self.model.supports_streaming_output):
+                        it = self.stream_batcher.open(sent, cs, chunk_padding)
+                    elif self.model.supports_streaming_output:
                         it = self.model.stream_synthesis(
                             sent, cs, chunk_padding
                         )
