@@ -97,6 +97,12 @@ std::vector<torch::Tensor> wsola_rows(torch::Tensor x, torch::Tensor in_len,
                                       torch::Tensor window, long half,
                                       long search, torch::Tensor gain,
                                       long N_out_max, long K_max);
+std::vector<torch::Tensor> wsola_stream_rows(
+    torch::Tensor x, std::vector<int64_t> par, std::vector<double> hop,
+    std::vector<double> gain, torch::Tensor carry, torch::Tensor tails,
+    torch::Tensor window, long half, long search, long N_out, long K_max);
+torch::Tensor resample_stream_rows(torch::Tensor x, std::vector<int64_t> par,
+                                   torch::Tensor carry, long N_out);
 // pcm.hip
 std::vector<torch::Tensor> pcm16_rows(torch::Tensor x, torch::Tensor len,
                                       long N_out, bool peak_normalize);
@@ -167,6 +173,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("n_frames"), py::arg("out_len"), py::arg("window"),
         py::arg("half"), py::arg("search"), py::arg("gain"),
         py::arg("n_out_max"), py::arg("k_max"));
+  m.def("wsola_stream_rows", &wsola_stream_rows,
+        "one round of per-row streaming WSOLA on carry ++ chunk; updates "
+        "carry and tails in place, returns (y, targets)",
+        py::arg("x"), py::arg("par"), py::arg("hop"), py::arg("gain"),
+        py::arg("carry"), py::arg("tails"), py::arg("window"),
+        py::arg("half"), py::arg("search"), py::arg("n_out"),
+        py::arg("k_max"));
+  m.def("resample_stream_rows", &resample_stream_rows,
+        "one round of per-row streaming linear resampling on carry ++ "
+        "chunk; updates carry in place, returns y",
+        py::arg("x"), py::arg("par"), py::arg("carry"), py::arg("n_out"));
   m.def("pcm16_rows", &pcm16_rows,
         "per-row peak-normalised int16 PCM of [B,N] f32/bf16; returns "
         "(pcm [B,n_out], peaks)",

@@ -82,6 +82,9 @@ class VitsVoice(SonataModel):
         self._tail_free: List[int] = []
         self._tails: Optional[torch.Tensor] = None
         self._ramp: Optional[torch.Tensor] = None
+        # device state of continuous stream prosody (ops.ProsodyStreamState),
+        # indexed by tail slot; allocated with the first stream that asks
+        self._prosody_state = None
         self._tashkeel = None
         if config.espeak_voice.startswith("ar"):
             from ..text.tashkeel import TashkeelModel
@@ -499,14 +502,23 @@ class VitsVoice(SonataModel):
     # ------------------------------------------------------------------ #
     @torch.no_grad()
     def stream_open(self, phonemes_batch: Sequence[str], chunk_size=45,
-                    chunk_padding: int = 3) -> List["StreamState"]:
+                    chunk_padding: int = 3,
+                    prosody=None) -> List["StreamState"]:
         """Encode a list of sentences in ONE batched encoder call and return
         one StreamState per sentence, to be advanced by stream_round.
         `chunk_size` is an int or one int per sentence.  Speaker and scales
         are those of the current synthesis config; seeds are per utterance,
         as in stream_synthesis.  Holds the inference lock for this call
-        only.  Release unfinished states with stream_close."""
+        only.  Release unfinished states with stream_close.
+        `prosody`: one (speed, volume, pitch) or None per sentence.  A
+        stream with a triple emits, over all its chunks, what
+        ops.apply_prosody_rows gives on its whole plain audio (frames * hop
+        samples, known here): the stretcher's state stays on the device
+        between rounds, and a round may emit an empty chunk."""
         B = len(phonemes_batch)
+        if prosody is None:
+            prosody = [None] * B
+        assert len(prosody) == B, "one prosody triple (or None) per sentence"
         if isinstance(chunk_size, int):
             chunk_size = [chunk_size] * B
         chunk_size = [int(c) for c in chunk_size]
@@ -543,22 +555,48 @@ class VitsVoice(SonataModel):
                 # one host sync: every row's frame count
                 frames = (y_mask[:, 0, :] > 0).sum(-1).tolist()
             slots = self._tail_slots_take(B)
+            if any(t is not None for t in prosody):
+                self._prosody_reserve()
+        from ..audio.prosody import StreamProsody
+
+        hop = self.net.arch.hop_length
         return [
             StreamState(
                 index=b, z=z, row=b, frames=int(frames[b]),
                 g=g[b : b + 1] if g is not None else None,
                 plan=chunk_plan(int(frames[b]), chunk_size[b], chunk_padding),
-                slot=slots[b])
+                slot=slots[b],
+                prosody=None if prosody[b] is None else StreamProsody(
+                    int(frames[b]) * hop, self.config.sample_rate,
+                    *prosody[b]))
             for b in range(B)]
+
+    def _prosody_reserve(self) -> None:
+        """Device state of stream prosody for every tail slot (cuda only;
+        on the CPU each StreamProsody keeps its own).  Called under
+        _infer_lock, like _tail_slots_take: rounds see either buffer
+        whole."""
+        if self.device.type != "cuda":
+            return
+        from ..ops import ProsodyStreamState
+
+        if self._prosody_state is None:
+            self._prosody_state = ProsodyStreamState(
+                self.config.sample_rate, self.device)
+        self._prosody_state.reserve(self._tails.shape[0])
 
     def stream_close(self, states) -> None:
         """Release the tail slots of states that will not be advanced any
-        further (finished states have released theirs already)."""
+        further (finished states have released theirs already).  The slot's
+        prosody state needs no cleaning: a stream's plan dies with it here,
+        and the next stream on the slot starts at frame 0 with an empty
+        carry, so it reads nothing the slot still holds."""
         with self._tail_lock:
             for s in states:
                 if s.slot is not None:
                     self._tail_free.append(s.slot)
                     s.slot = None
+                s.prosody = None
                 s.done = True
 
     def _tail_slots_take(self, n: int) -> List[int]:
@@ -588,7 +626,8 @@ class VitsVoice(SonataModel):
         seam (-> pcm) and the copy of the packed rows to the host.  Caller
         holds _infer_lock.  Returns what _round_collect needs, or None when
         no state is live."""
-        from ..ops import gather_windows, pcm16_rows, stream_seam_rows
+        from ..ops import (gather_windows, pcm16_rows, prosody_stream_rows,
+                           stream_seam_rows)
 
         live = [s for s in states if not s.done]
         if not live:
@@ -626,6 +665,14 @@ class VitsVoice(SonataModel):
                 wav, lo, hi, ext, [s.prev_ext for s in live],
                 [s.slot for s in live], self._tails, self._ramp,
                 tails_out=self._tails)
+            if any(s.prosody is not None for s in live):
+                if self._prosody_state is not None:
+                    # slots taken by prosody-free opens since the last grow
+                    self._prosody_state.reserve(self._tails.shape[0])
+                out, out_len = prosody_stream_rows(
+                    out, out_len, [s.prosody for s in live],
+                    [s.slot for s in live], self._prosody_state,
+                    last=[sp.is_last for sp in specs])
             if pcm:
                 out, _ = pcm16_rows(out, out_len)
         finished = []
@@ -678,6 +725,8 @@ class VitsVoice(SonataModel):
         per stream on the device, copy the packed rows to the host once.
         Returns [(state, chunk)] for the states that were live: float32
         chunks, or int16 (ops.pcm16_rows of the float chunk) with pcm=True.
+        A state opened with a prosody triple has it applied before the copy
+        (and before the PCM conversion); its chunk may then be empty.
         A state whose chunk was its last is finished (state.done).  Holds
         the inference lock for the round only, and always decodes eagerly
         (R and the window length change from round to round)."""
@@ -690,15 +739,19 @@ class VitsVoice(SonataModel):
 
     def stream_synthesis_batch(self, phonemes_batch: Sequence[str],
                                chunk_size=45, chunk_padding: int = 3,
-                               pcm: bool = False):
+                               pcm: bool = False, prosody=None):
         """stream_synthesis for a list of sentences at once: yields (index,
         chunk) with, per index, the chunk boundaries, total length and seams
         of stream_synthesis.  One encoder call, then one decode per round
         for all streams still running.  On cuda round r+1 is enqueued before
         round r's host copy is consumed (the first round is emitted first).
         The inference lock is held per call and per round, never across a
-        yield; closing the iterator releases the streams' slots."""
-        states = self.stream_open(phonemes_batch, chunk_size, chunk_padding)
+        yield; closing the iterator releases the streams' slots.
+        `prosody` is stream_open's: with a triple, an index's chunks
+        concatenate to the one-shot prosody of its plain stream, and a chunk
+        may be empty (every live stream still yields one per round)."""
+        states = self.stream_open(phonemes_batch, chunk_size, chunk_padding,
+                                  prosody=prosody)
         pins = _PinnedPair() if self.device.type == "cuda" else None
         try:
             with self._infer_lock:
@@ -728,15 +781,16 @@ class StreamState:
     its previous chunk left."""
 
     __slots__ = ("index", "z", "row", "frames", "g", "slot", "prev_ext",
-                 "done", "_plan", "_next")
+                 "done", "prosody", "_plan", "_next")
 
-    def __init__(self, index, z, row, frames, g, plan, slot):
+    def __init__(self, index, z, row, frames, g, plan, slot, prosody=None):
         self.index = index
         self.z = z
         self.row = row
         self.frames = frames
         self.g = g
         self.slot = slot
+        self.prosody = prosody  # audio.prosody.StreamProsody or None
         self.prev_ext = 0
         self.done = False
         self._plan = plan

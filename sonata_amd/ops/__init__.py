@@ -77,4 +77,8 @@ from .functional import (  # noqa: F401,E402
     pcm16_rows,
     gather_windows,
     stream_seam_rows,
+    ProsodyStreamState,
+    resample_stream_rows,
+    wsola_stream_rows,
+    prosody_stream_rows,
 )

@@ -962,3 +962,177 @@ def stream_seam_rows(wav: torch.Tensor, lo, hi, ext, prev_ext, slot,
     out = hext.stream_seam_rows(wav, lo, hi, ex, pe, slot, tails_in,
                                 tails_out, ramp, n_out)
     return out, out_lengths, tails_out
+
+
+# --------------------------------------------------------------------------- #
+# streaming prosody (csrc/prosody.hip, the *_stream_rows kernels): rate /
+# pitch / volume for realtime streams, one launch per stage per round for all
+# live streams, state on the device indexed by the streams' tail slots.  The
+# rules and every length come from audio.prosody (StreamProsodyPlan);
+# StreamProsody.push row by row is the CPU path and the oracle.
+# --------------------------------------------------------------------------- #
+class ProsodyStreamState:
+    """Device state of streaming prosody for one sample rate, indexed by
+    slot: per WSOLA stage (0: the pitch chain's stretch, 1: speed) a carry of
+    seg_cap samples and the half-frame tail of the last chosen frame, plus
+    the resample stage's one-sample carry.  A stream's first push names no
+    carry and no tail, so a slot needs no cleaning between streams."""
+
+    def __init__(self, sample_rate: int, device):
+        from ..audio import prosody as P
+        from ..audio.window import hann_window
+
+        self.sample_rate = int(sample_rate)
+        self.device = torch.device(device)
+        self.frame, self.half, self.search = P.wsola_plan(
+            0, 1.0, sample_rate)[:3]
+        self.seg_cap = _round_up(
+            P.wsola_seg_cap(self.frame, self.search), 4)
+        # the host's own window, bit for bit (never recomputed on the device)
+        self.window = torch.from_numpy(
+            hann_window(self.frame).copy()).to(self.device)
+        self.slots = 0
+        self.rs_carry = None
+        self.carry = [None, None]
+        self.tails = [None, None]
+
+    def reserve(self, slots: int) -> None:
+        """Grow to at least `slots` slots, keeping what live streams hold."""
+        from ..audio.prosody import RESAMPLE_CARRY
+
+        if slots <= self.slots:
+            return
+
+        def grown(old, width):
+            new = torch.zeros((slots, width), dtype=torch.float32,
+                              device=self.device)
+            if old is not None:
+                new[: old.shape[0]].copy_(old)
+            return new
+
+        self.rs_carry = grown(self.rs_carry, RESAMPLE_CARRY)
+        self.carry = [grown(c, self.seg_cap) for c in self.carry]
+        self.tails = [grown(t, self.half) for t in self.tails]
+        self.slots = slots
+
+
+def resample_stream_rows(x: torch.Tensor, lengths, pushes, slots,
+                         carry: torch.Tensor):
+    """One round of the streaming resample stage on the device.  x [R, N]
+    f32 chunk rows of lengths[r] samples; pushes[r] is the
+    audio.prosody.ResamplePush of the row's plan, or None for a row that is
+    copied; carry f32 [S, 1] is updated in place at slots[r].  Returns
+    (y [R, n_out] zero-padded, n_out a multiple of 8, out_lengths)."""
+    R = x.shape[0]
+    lens = _row_lengths(lengths, R)
+    slots = _per_row_int(slots, R)
+    par, out = [], []
+    for n, p, s in zip(lens, pushes, slots):
+        if p is None or p.copy:
+            par += [s, n, 0, 0, 0, n, n, 0, n, 1, n, 0]
+            out.append(n)
+            continue
+        assert p.m == n, "the plan was pushed another length"
+        par += [s, p.m, p.a0, p.in_pos, p.carry_len, p.n, p.n_out, p.e0,
+                p.e1, 0, p.keep_pos, p.keep_len]
+        out.append(p.e1 - p.e0)
+    n_out = max(_round_up(max(out, default=0), 8), 8)
+    y = hip_ext(required=True).resample_stream_rows(
+        x.contiguous(), par, carry, n_out)
+    return y, torch.tensor(out, dtype=torch.long)
+
+
+def wsola_stream_rows(x: torch.Tensor, lengths, pushes, slots,
+                      carry: torch.Tensor, tails: torch.Tensor,
+                      window: torch.Tensor, half: int, search: int,
+                      gain=None, return_targets: bool = False):
+    """One round of a streaming WSOLA stage on the device.  x [R, N] f32
+    chunk rows of lengths[r] samples; pushes[r] is the
+    audio.prosody.WsolaPush of the row's plan, or None for a row that is
+    copied (and scaled by gain[r]); carry f32 [S, seg_cap] and tails f32
+    [S, half] are updated in place at slots[r].  Returns (y [R, n_out]
+    zero-padded, n_out a multiple of 8, out_lengths[, targets [R, K] i32:
+    the global start of each frame run this round, -1 in unused slots])."""
+    R = x.shape[0]
+    lens = _row_lengths(lengths, R)
+    slots = _per_row_int(slots, R)
+    gains = _per_row(gain, R)
+    par, hop, out, nks = [], [], [], [1]
+    for n, p, s in zip(lens, pushes, slots):
+        if p is None or p.passthrough:
+            par += [s, n, 0, 0, 0, 0, 0, n, 0, n, 1, n, 0]
+            hop.append(1.0)
+            out.append(n)
+            continue
+        assert p.m == n, "the plan was pushed another length"
+        par += [s, p.m, p.a0, p.in_pos, p.carry_len, p.k0, p.nk, p.n, p.e0,
+                p.e1, 2 if p.closing else 0, p.keep_pos, p.keep_len]
+        hop.append(p.ana_hop)
+        out.append(p.e1 - p.e0)
+        nks.append(p.nk)
+    n_out = max(_round_up(max(out, default=0), 8), 8)
+    y, targets = hip_ext(required=True).wsola_stream_rows(
+        x.contiguous(), par, hop, gains, carry, tails, window, half, search,
+        n_out, max(nks))
+    out = torch.tensor(out, dtype=torch.long)
+    return (y, out, targets) if return_targets else (y, out)
+
+
+def prosody_stream_rows(x: torch.Tensor, lengths, procs, slots,
+                        state: Optional[ProsodyStreamState], last=None):
+    """One round of streaming prosody for R streams: x [R, N] f32 holds each
+    stream's next plain chunk (lengths[r] samples), procs[r] its
+    audio.prosody.StreamProsody (None: the row is copied), slots[r] its slot
+    in `state`, last[r] whether this is the stream's final chunk.  Returns
+    (y [R, n_out] zero-padded, n_out a multiple of 8, out_lengths); a row
+    may emit nothing this round.  Per row the stages are those of
+    apply_prosody_rows on that row alone: resample by pitch, WSOLA by
+    1/pitch, WSOLA by speed, the gain in the row's last stage (a volume-only
+    row is scaled).  On the CPU each row goes through StreamProsody.push."""
+    R = x.shape[0]
+    lens = _row_lengths(lengths, R)
+    last = [False] * R if last is None else [bool(v) for v in last]
+    assert len(procs) == R and len(last) == R
+    if not use_hip(x):
+        import numpy as np
+
+        xn = x.detach().cpu().numpy()
+        rows = [xn[r, : lens[r]].copy() if procs[r] is None
+                else procs[r].push(xn[r, : lens[r]], last[r])
+                for r in range(R)]
+        out = [int(r.shape[0]) for r in rows]
+        y = np.zeros((R, max(_round_up(max(out, default=0), 8), 8)),
+                     dtype=np.float32)
+        for r, row in enumerate(rows):
+            y[r, : out[r]] = row
+        return (torch.from_numpy(y).to(x.device),
+                torch.tensor(out, dtype=torch.long))
+    assert state is not None, "device streams need a ProsodyStreamState"
+    plans = [None if p is None or p.plan.is_noop else p.plan for p in procs]
+    steps = [None if pl is None else pl.push(n, l)
+             for pl, n, l in zip(plans, lens, last)]
+    y, cur = x, torch.tensor(lens, dtype=torch.long)
+    if not any(pl is not None for pl in plans):
+        return y, cur
+    slots = _per_row_int(slots, R)
+    assert max(slots) < state.slots, "slot outside the reserved state"
+    if any(pl is not None and pl.do_pitch for pl in plans):
+        y, cur = resample_stream_rows(
+            y, cur, [s.resample if s else None for s in steps], slots,
+            state.rs_carry)
+        y, cur = wsola_stream_rows(
+            y, cur, [s.wsola_pitch if s else None for s in steps], slots,
+            state.carry[0], state.tails[0], state.window, state.half,
+            state.search,
+            gain=[pl.gain if pl is not None and pl.do_pitch
+                  and not pl.do_speed else 1.0 for pl in plans])
+    if any(pl is not None and (pl.do_speed or not pl.do_pitch)
+           for pl in plans):
+        y, cur = wsola_stream_rows(
+            y, cur, [s.wsola_speed if s else None for s in steps], slots,
+            state.carry[1], state.tails[1], state.window, state.half,
+            state.search,
+            gain=[pl.gain if pl is not None
+                  and (pl.do_speed or not pl.do_pitch) else 1.0
+                  for pl in plans])
+    return y, cur

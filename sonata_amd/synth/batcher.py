@@ -132,10 +132,12 @@ class _StreamHandle:
     once opened, its model state."""
 
     __slots__ = ("phonemes", "chunk_size", "chunk_padding", "pcm", "q",
-                 "cancelled", "state")
+                 "cancelled", "state", "prosody")
 
-    def __init__(self, phonemes, chunk_size, chunk_padding, pcm):
+    def __init__(self, phonemes, chunk_size, chunk_padding, pcm,
+                 prosody=None):
         self.phonemes = phonemes
+        self.prosody = tuple(prosody) if prosody is not None else None
         self.chunk_size = int(chunk_size)
         self.chunk_padding = int(chunk_padding)
         self.pcm = bool(pcm)
@@ -207,13 +209,18 @@ class StreamBatcher:
         self._worker.start()
 
     def open(self, phonemes: str, chunk_size: int = 45,
-             chunk_padding: int = 3, pcm: bool = False):
+             chunk_padding: int = 3, pcm: bool = False, prosody=None):
         """Start one stream; returns the iterator of its chunks (float32
         arrays, or int16 with pcm=True), those model.stream_synthesis
-        yields for the same arguments."""
+        yields for the same arguments.
+        `prosody`: optional (speed, volume, pitch) applied continuously
+        over the stream by the model (stream_open(prosody=...)); streams of
+        one round may each carry their own.  The chunks then concatenate to
+        the one-shot prosody of the plain stream; rounds in which the
+        stretcher emits nothing yield no chunk."""
         if self._closed:
             raise RuntimeError("stream batcher closed")
-        h = _StreamHandle(phonemes, chunk_size, chunk_padding, pcm)
+        h = _StreamHandle(phonemes, chunk_size, chunk_padding, pcm, prosody)
         self._q.put(h)
         return _StreamIter(h)
 
@@ -265,9 +272,11 @@ class StreamBatcher:
         for pad in sorted({h.chunk_padding for h in new}):
             group = [h for h in new if h.chunk_padding == pad]
             try:
+                kw = {"prosody": [h.prosody for h in group]} if any(
+                    h.prosody is not None for h in group) else {}
                 states = self.model.stream_open(
                     [h.phonemes for h in group],
-                    [h.chunk_size for h in group], pad)
+                    [h.chunk_size for h in group], pad, **kw)
             except BaseException as e:  # noqa: BLE001 - reaches the callers
                 self._fail(group, e)
                 continue
@@ -305,7 +314,9 @@ class StreamBatcher:
             return []
         by_state = {id(h.state): h for h in bucket}
         for state, chunk in chunks:
-            by_state[id(state)].q.put(chunk)
+            h = by_state[id(state)]
+            if len(chunk) or h.prosody is None:
+                h.q.put(chunk)
         still = []
         for h in bucket:
             if h.state.done:

@@ -118,6 +118,17 @@ class SonataSpeechSynthesizer:
         # synthesize_streamed opens its sentences through it, so concurrent
         # realtime streams share chunk decodes
         self.stream_batcher = None
+        # prosody of synthesize_streamed: "chunk" applies the output config
+        # to every chunk on its own, on the host (the reference's
+        # behaviour); "continuous" hands the triple to the model's stream
+        # path, which stretches the sentence as a whole with its state kept
+        # between chunks (on the device for a cuda voice)
+        self.stream_prosody = os.environ.get("SONATA_STREAM_PROSODY",
+                                             "chunk") or "chunk"
+        if self.stream_prosody not in ("chunk", "continuous"):
+            raise ValueError(
+                "SONATA_STREAM_PROSODY must be 'chunk' or 'continuous', "
+                f"not {self.stream_prosody!r}")
 
     # ------------------------------------------------------------------ #
     def audio_output_info(self) -> AudioInfo:
@@ -235,11 +246,23 @@ class SonataSpeechSynthesizer:
         """Realtime mode: producer thread pushes waveform chunks through a
         queue while the caller consumes (reference RealtimeSpeechStream,
         synth/src/lib.rs:335-430).  Chunk size grows per processed chunk
-        (:352-356).  Yields float32 sample chunks."""
+        (:352-356).  Yields float32 sample chunks.
+        With stream_prosody == "continuous" (and a model with batched
+        streams) rate / pitch / volume run inside the model's stream path:
+        a sentence's chunks concatenate to its one-shot prosody, nothing is
+        applied here and empty chunks are dropped."""
         phonemes = self.model.phonemize_text(text)
         info = self.model.audio_output_info()
         q: "queue.Queue" = queue.Queue()
         DONE, ERROR = object(), object()
+        if self.stream_prosody not in ("chunk", "continuous"):
+            raise ValueError(f"stream_prosody {self.stream_prosody!r}")
+        triple = None
+        if (self.stream_prosody == "continuous" and output_config is not None
+                and not output_config.is_noop
+                and self.model.supports_streaming_output
+                and hasattr(self.model, "stream_synthesis_batch")):
+            triple = output_config.prosody_triple()
 
         def producer():
             try:
@@ -254,7 +277,16 @@ class SonataSpeechSynthesizer:
                     # (faster) chunks; the in-sentence chunker grows
                     # further.  The 1024 cap matches MAX_CHUNK_SIZE.
                     cs = min(chunk_size * (n_done + 1), 1024)
-                    if (self.stream_batcher is not None
+                    if triple is not None:
+                        if self.stream_batcher is not None:
+                            it = self.stream_batcher.open(
+                                sent, cs, chunk_padding, prosody=triple)
+                        else:
+                            it = (c for _, c in
+                                  self.model.stream_synthesis_batch(
+                                      [sent], cs, chunk_padding,
+                                      prosody=[triple]))
+                    elif (self.stream_batcher is not None
                             and self.model.supports_streaming_output):
                         it = self.stream_batcher.open(sent, cs, chunk_padding)
                     elif self.model.supports_streaming_output:
@@ -264,6 +296,10 @@ class SonataSpeechSynthesizer:
                     else:
                         it = iter([self.model.speak_one_sentence(sent).samples])
                     for chunk in it:
+                        if triple is not None:
+                            if len(chunk):
+                                q.put(chunk)
+                            continue
                         if output_config is not None and not output_config.is_noop:
                             chunk = output_config.apply(chunk, info.sample_rate)
                         q.put(chunk)
