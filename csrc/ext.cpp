@@ -107,6 +107,11 @@ torch::Tensor resample_stream_rows(torch::Tensor x, std::vector<int64_t> par,
 std::vector<torch::Tensor> pcm16_rows(torch::Tensor x, torch::Tensor len,
                                       long N_out, bool peak_normalize);
 long pcm_tile();
+// resample.hip
+torch::Tensor resample_poly_rows(torch::Tensor x, torch::Tensor in_len,
+                                 torch::Tensor out_len, torch::Tensor bank,
+                                 long L, long M, long H, long n_out);
+long resample_tile();
 // stream.hip
 torch::Tensor gather_windows(std::vector<torch::Tensor> zs,
                              std::vector<int64_t> src,
@@ -190,6 +195,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("len"), py::arg("n_out"),
         py::arg("peak_normalize") = true);
   m.attr("PCM_TILE") = pcm_tile();
+  m.def("resample_poly_rows", &resample_poly_rows,
+        "per-row polyphase FIR sample-rate conversion of [B,N] f32/bf16 by "
+        "L/M; bank is the [K][L] f32 filter; returns y [B,n_out] f32",
+        py::arg("x"), py::arg("in_len"), py::arg("out_len"), py::arg("bank"),
+        py::arg("L"), py::arg("M"), py::arg("H"), py::arg("n_out"));
+  m.attr("RESAMPLE_TILE") = resample_tile();
   m.def("gather_windows", &gather_windows,
         "pack ragged latent windows of several [b,C,F] sources into "
         "[R,C,l_max], zero padded; one launch",

@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "csrc/attention_cl.hip",
         "csrc/prosody.hip",
         "csrc/pcm.hip",
+        "csrc/resample.hip",
         "csrc/stream.hip",
         "csrc/engine/vits_engine.cpp",
     ],

@@ -184,6 +184,13 @@ class SonataModel(abc.ABC):
         prosody=None, silence_ms=None) -> List[PcmAudio]."""
         return False
 
+    @property
+    def supports_output_rate(self) -> bool:
+        """True when speak_batch / speak_batch_pcm take sample_rate= (one
+        int, or one int-or-None per row) and return each row converted to
+        its rate, with AudioInfo(sample_rate=<its rate>)."""
+        return False
+
     # -- synthesis config (reference get/set_fallback..., typed not Any) ---- #
     @abc.abstractmethod
     def get_synthesis_config(self):

@@ -39,6 +39,7 @@ class SynthesisRequest:
     pitch: Optional[float] = None
     volume: Optional[float] = None
     appended_silence_ms: Optional[float] = None
+    sample_rate: Optional[int] = None
 
     @staticmethod
     def from_json(line: str) -> "SynthesisRequest":
@@ -53,6 +54,7 @@ class SynthesisRequest:
             pitch=d.get("pitch"),
             volume=d.get("volume"),
             appended_silence_ms=d.get("appended_silence_ms"),
+            sample_rate=d.get("sample_rate"),
         )
 
 
@@ -79,6 +81,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("-v", "--volume", type=float, default=None)
     p.add_argument("--silence", type=float, default=None,
                    help="appended silence ms after each sentence")
+    p.add_argument("--sample-rate", type=int, default=None,
+                   help="output sample rate in Hz (default: the voice's own)")
     p.add_argument("--chunk-size", type=int, default=100,
                    help="realtime first-chunk mel frames (reference default)")
     p.add_argument("--chunk-padding", type=int, default=3)
@@ -103,10 +107,14 @@ def _make_output_config(args, req: SynthesisRequest):
     volume = req.volume if req.volume is not None else args.volume
     silence = (req.appended_silence_ms if req.appended_silence_ms is not None
                else args.silence)
-    if rate is None and pitch is None and volume is None and silence is None:
+    sample_rate = (req.sample_rate if req.sample_rate is not None
+                   else getattr(args, "sample_rate", None))
+    if rate is None and pitch is None and volume is None and silence is None \
+            and sample_rate is None:
         return None
     return AudioOutputConfig(rate=rate, volume=volume, pitch=pitch,
-                             appended_silence_ms=silence)
+                             appended_silence_ms=silence,
+                             sample_rate=sample_rate)
 
 
 def _apply_synth_config(voice, args, req: SynthesisRequest) -> None:
@@ -134,6 +142,10 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
     _apply_synth_config(synth.model, args, req)
     out_cfg = _make_output_config(args, req)
     info = synth.audio_output_info()
+    # WAV headers carry the result's own rate
+    out_rate = (int(out_cfg.sample_rate)
+                if out_cfg is not None and out_cfg.sample_rate
+                else info.sample_rate)
     total = 0
     if args.output_file:
         path = _enumerate_path(args.output_file, n)
@@ -151,7 +163,7 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
             from ..audio.wav import wav_header
 
             header_pos = stdout.tell() if stdout.seekable() else None
-            stdout.write(wav_header(0, info.sample_rate))
+            stdout.write(wav_header(0, out_rate))
             for chunk in synth.synthesize_streamed(
                     req.text, out_cfg, args.chunk_size, args.chunk_padding):
                 stdout.write(to_i16_bytes(chunk, peak_normalize=False))
@@ -160,7 +172,7 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
             if header_pos is not None:
                 end = stdout.tell()
                 stdout.seek(header_pos)
-                stdout.write(wav_header(total * 2, info.sample_rate))
+                stdout.write(wav_header(total * 2, out_rate))
                 stdout.seek(end)
             stdout.flush()
             return total
@@ -172,7 +184,7 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
             samples = (np.concatenate(parts) if parts
                        else np.zeros(0, dtype=np.float32))
         total = len(samples)
-        stdout.write(wav_bytes(samples, info.sample_rate))
+        stdout.write(wav_bytes(samples, out_rate))
         stdout.flush()
     return total
 

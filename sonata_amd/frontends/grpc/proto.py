@@ -117,6 +117,7 @@ def _build_file() -> descriptor_pb2.FileDescriptorProto:
         (2, "volume", "uint32", "optional"),
         (3, "pitch", "uint32", "optional"),
         (4, "appended_silence_ms", "uint32", "optional"),
+        (5, "sample_rate", "uint32", "optional"),
     ])
     message("Utterance", [
         (1, "voice_id", "string", None),

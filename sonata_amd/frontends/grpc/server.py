@@ -136,10 +136,22 @@ class SonataGrpcService:
             appended_silence_ms=(args.appended_silence_ms
                                  if args.HasField("appended_silence_ms")
                                  else None),
+            sample_rate=(args.sample_rate if args.HasField("sample_rate")
+                         else None),
         )
-        if cfg.is_noop and cfg.appended_silence_ms is None:
+        if cfg.is_noop and cfg.appended_silence_ms is None \
+                and cfg.sample_rate is None:
             return None
         return cfg
+
+    @staticmethod
+    def _output_rate(v, out_cfg, context) -> Optional[int]:
+        """The request's output rate when it differs from the voice's own;
+        a rate the filter does not serve ends the RPC."""
+        try:
+            return v.synth.output_rate(out_cfg)
+        except ValueError as e:
+            context.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
 
     # ------------------------------------------------------------------ #
     # RPC implementations
@@ -205,6 +217,7 @@ class SonataGrpcService:
         v = self._get(request.voice_id, context)
         out_cfg = self._speech_args_to_config(
             request.speech_args if request.HasField("speech_args") else None)
+        rate = self._output_rate(v, out_cfg, context)
         mode = request.synthesis_mode
         if mode == MODE_LAZY:
             it = v.synth.synthesize_lazy(request.text, out_cfg, pcm=True)
@@ -225,13 +238,16 @@ class SonataGrpcService:
         # the voice can) unless prosody has to run on the host's floats
         pcm = out_cfg is None or out_cfg.is_noop or on_device
         silence_ms = out_cfg.appended_silence_ms if out_cfg else None
+        # the output rate rides along too; after host prosody it is
+        # applied on the host as well
         futures = [v.batcher.submit(sent, triple, pcm=pcm,
-                                    silence_ms=silence_ms if pcm else None)
+                                    silence_ms=silence_ms if pcm else None,
+                                    sample_rate=rate if pcm else None)
                    for sent in sentences]
         for f in futures:
             audio = f.result()
             if not pcm:
-                audio = v.synth.to_pcm(audio, out_cfg)
+                audio = v.synth.to_pcm(audio, out_cfg, rate=rate)
             yield MESSAGES["SynthesisResult"](
                 wav_samples=audio.as_wave_bytes(),
                 rtf=float(audio.real_time_factor),
@@ -243,6 +259,7 @@ class SonataGrpcService:
             request.speech_args if request.HasField("speech_args") else None)
         from ...audio.samples import to_i16_bytes
 
+        self._output_rate(v, out_cfg, context)
         for chunk in v.synth.synthesize_streamed(
                 request.text, out_cfg,
                 REALTIME_CHUNK_SIZE, REALTIME_CHUNK_PADDING):

@@ -35,15 +35,18 @@ class AudioOutputConfig:
     def __init__(self, rate: Optional[float] = None,
                  volume: Optional[float] = None,
                  pitch: Optional[float] = None,
-                 appended_silence_ms: Optional[float] = None):
+                 appended_silence_ms: Optional[float] = None,
+                 sample_rate: Optional[int] = None):
         self.rate = rate
         self.volume = volume
         self.pitch = pitch
         self.appended_silence_ms = appended_silence_ms
+        self.sample_rate = sample_rate  # Hz; None: the voice's own rate
 
     def _to_internal(self) -> _OutCfg:
         return _OutCfg(rate=self.rate, volume=self.volume, pitch=self.pitch,
-                       appended_silence_ms=self.appended_silence_ms)
+                       appended_silence_ms=self.appended_silence_ms,
+                       sample_rate=self.sample_rate)
 
 
 class WaveSamples:

@@ -214,14 +214,61 @@ class VitsVoice(SonataModel):
         infer_ms = (time.perf_counter() - t0) * 1000.0
         return audio, audio_lengths, infer_ms
 
+    @property
+    def supports_output_rate(self) -> bool:
+        """speak_batch / speak_batch_pcm take sample_rate= and convert each
+        row to its rate on the model's device (ops.resample_rows)."""
+        return True
+
+    def _row_rates(self, sample_rate, B: int) -> List[int]:
+        """One output rate per row (None: the voice's own), each checked
+        against the filter's limits."""
+        from ..audio.resample import check_rate, is_identity
+
+        native = self.config.sample_rate
+        if sample_rate is None or isinstance(sample_rate, int):
+            sample_rate = [sample_rate] * B
+        assert len(sample_rate) == B, "one sample rate per row"
+        rates = []
+        for r in sample_rate:
+            if is_identity(native, r):
+                rates.append(native)
+            else:
+                check_rate(native, r)
+                rates.append(int(r))
+        return rates
+
+    def _resample_groups(self, audio2d, audio_lengths, rates):
+        """ops.resample_rows once per distinct rate, on that rate's rows.
+        Yields (rate, row indices, y [b, n], out_lengths); rows at the
+        voice's own rate pass through untouched."""
+        from ..ops import resample_rows
+
+        lens = [int(n) for n in audio_lengths.tolist()]
+        for rate in sorted(set(rates)):
+            idx = [b for b, r in enumerate(rates) if r == rate]
+            if len(idx) == len(rates):
+                rows, rl = audio2d, lens
+            else:
+                sel = torch.tensor(idx, dtype=torch.long,
+                                   device=audio2d.device)
+                rl = [lens[b] for b in idx]
+                rows = audio2d.index_select(0, sel)[:, : max(rl, default=0)]
+            y, out_lengths = resample_rows(
+                rows, rl, self.config.sample_rate, rate)
+            yield rate, idx, y, out_lengths
+
     @torch.no_grad()
     def speak_batch(self, phonemes_batch: Sequence[str],
-                    prosody=None) -> List[Audio]:
+                    prosody=None, sample_rate=None) -> List[Audio]:
         """True padded [B, T] batching (the reference loops batch=1:
         piper/src/lib.rs:425-437 — batching is a headline improvement).
 
         `prosody`: optional per-row sequence of (speed, volume, pitch) or
-        None; applied on the device tensor before the single host copy."""
+        None; applied on the device tensor before the single host copy.
+        `sample_rate`: optional output rate, one int or one int-or-None per
+        row; each distinct rate is converted on the device after prosody
+        (ops.resample_rows) and copied on its own."""
         audio, audio_lengths, infer_ms = self._infer_batch(phonemes_batch)
         B = len(phonemes_batch)
         info = self.audio_output_info()
@@ -229,6 +276,17 @@ class VitsVoice(SonataModel):
         if prosody is not None:
             audio, audio_lengths = self._prosody_rows(
                 audio, audio_lengths, prosody)
+        rates = self._row_rates(sample_rate, B)
+        if any(r != info.sample_rate for r in rates):
+            out = [None] * B
+            for rate, idx, y, out_lengths in self._resample_groups(
+                    audio[:, 0, :], audio_lengths, rates):
+                y = y.float().cpu().numpy()
+                rinfo = AudioInfo(sample_rate=rate)
+                for i, b in enumerate(idx):
+                    out[b] = Audio(y[i, : int(out_lengths[i])], rinfo,
+                                   inference_ms=infer_ms / B)
+            return out
         audio = audio.float().cpu().numpy()
         audio_lengths = audio_lengths.cpu().numpy()
         for b in range(B):
@@ -248,25 +306,32 @@ class VitsVoice(SonataModel):
 
     @torch.no_grad()
     def speak_batch_pcm(self, phonemes_batch: Sequence[str], prosody=None,
-                        silence_ms=None) -> List[PcmAudio]:
+                        silence_ms=None, sample_rate=None) -> List[PcmAudio]:
         """speak_batch whose results are wire-format int16: what
         `Audio.as_wave_bytes` gives for speak_batch's samples with
         `silence_ms` of silence merged on (per row or one value; rounded to
-        samples as generate_silence does).  On cuda the order is optional
-        device prosody, ops.pcm16_rows, then ONE host copy of the int16
-        batch: half the bytes of the float copy, and no per-row NumPy
-        passes.  A CPU voice, or SONATA_DEVICE_PCM=0, converts
+        samples as generate_silence does, at the row's output rate).  On
+        cuda the order is optional device prosody, optional
+        ops.resample_rows, ops.pcm16_rows, then ONE host copy of the int16
+        batch per distinct rate: half the bytes of the float copy, and no
+        per-row NumPy passes.  A CPU voice, or SONATA_DEVICE_PCM=0, converts
         speak_batch's samples on the host: same bytes."""
         B = len(phonemes_batch)
         if silence_ms is None or isinstance(silence_ms, (int, float)):
             silence_ms = [silence_ms] * B
         assert len(silence_ms) == B, "one silence value per row"
-        sil = [silence_samples(ms, self.config.sample_rate) if ms else 0
-               for ms in silence_ms]
+        rates = self._row_rates(sample_rate, B)
+        native = self.config.sample_rate
+        converts = any(r != native for r in rates)
+        sil = [silence_samples(ms, r) if ms else 0
+               for ms, r in zip(silence_ms, rates)]
         if not self._device_pcm():
-            audios = (self.speak_batch(phonemes_batch, prosody=prosody)
-                      if prosody is not None
-                      else self.speak_batch(phonemes_batch))
+            kw = {}
+            if prosody is not None:
+                kw["prosody"] = prosody
+            if converts:
+                kw["sample_rate"] = rates
+            audios = self.speak_batch(phonemes_batch, **kw)
             return [PcmAudio.from_audio(a, s) for a, s in zip(audios, sil)]
         from ..ops import pcm16_rows
 
@@ -274,6 +339,18 @@ class VitsVoice(SonataModel):
         if prosody is not None:
             audio, audio_lengths = self._prosody_rows(
                 audio, audio_lengths, prosody)
+        if converts:
+            out = [None] * B
+            for rate, idx, y, out_lengths in self._resample_groups(
+                    audio[:, 0, :], audio_lengths, rates):
+                pcm, pcm_lengths = pcm16_rows(y, out_lengths,
+                                              [sil[b] for b in idx])
+                pcm = pcm.cpu().numpy()
+                rinfo = AudioInfo(sample_rate=rate)
+                for i, b in enumerate(idx):
+                    out[b] = PcmAudio(pcm[i, : int(pcm_lengths[i])], rinfo,
+                                      inference_ms=infer_ms / B)
+            return out
         # bf16 decoder output is read as it is (widening is exact)
         pcm, out_lengths = pcm16_rows(audio[:, 0, :], audio_lengths, sil)
         pcm = pcm.cpu().numpy()

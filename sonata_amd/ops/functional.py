@@ -14,6 +14,7 @@ LeakyReLU (MFMA conv-as-GEMM).
 
 from __future__ import annotations
 
+import threading
 from typing import Optional
 
 import torch
@@ -846,6 +847,59 @@ def pcm16_rows(x: torch.Tensor, lengths, silence=None,
     pcm, _peaks = ext.pcm16_rows(x, _i32(lens, x.device), n_out,
                                  bool(peak_normalize))
     return pcm, out_lengths
+
+
+# --------------------------------------------------------------------------- #
+# batched output sample-rate conversion (csrc/resample.hip): the polyphase
+# FIR of audio.resample on [B, N] f32 / bf16 rows.  The CPU path calls
+# audio.resample.resample_poly row by row and is the oracle; the kernel adds
+# the same products in f32 and stays within K * 2^-23 * S * max|x| of it.
+# --------------------------------------------------------------------------- #
+RESAMPLE_TILE = 256  # outputs per workgroup (csrc/resample.hip)
+
+_RESAMPLE_BANKS: dict = {}
+_RESAMPLE_BANKS_LOCK = threading.Lock()
+
+
+def _resample_bank(d, device) -> torch.Tensor:
+    """The filter in the kernel's [K][L] layout, uploaded once per rate pair
+    and device."""
+    key = (d.rate_in, d.rate_out, str(device))
+    with _RESAMPLE_BANKS_LOCK:
+        bank = _RESAMPLE_BANKS.get(key)
+        if bank is None:
+            import numpy as np
+
+            flat = np.ascontiguousarray(d.bank.T).reshape(-1)
+            bank = torch.from_numpy(flat.copy()).to(device)
+            _RESAMPLE_BANKS[key] = bank
+    return bank
+
+
+def resample_rows(x: torch.Tensor, lengths, rate_in: int, rate_out):
+    """Rows of x [B, N] (f32 or bf16) with lengths[b] samples at rate_in ->
+    f32 rows at rate_out, as audio.resample.resample_poly gives them.
+    Returns (y [B, max out_len] zero-padded, out_lengths).  rate_out equal
+    to rate_in, or None, is the identity: x itself and no launch."""
+    from ..audio import resample as R
+
+    B = x.shape[0]
+    lens = _row_lengths(lengths, B)
+    assert all(0 <= n <= x.shape[1] for n in lens), "length outside the row"
+    if R.is_identity(rate_in, rate_out):
+        return x, torch.tensor(lens, dtype=torch.long)
+    d = R.design(rate_in, rate_out)
+    out = [-(-n * d.L // d.M) for n in lens]
+    if not use_hip(x):
+        xn = x.detach().float().cpu().numpy()
+        return _rows_from_numpy(
+            [R.resample_poly(xn[b, : lens[b]], rate_in, rate_out)
+             for b in range(B)], x.device)
+    ext = hip_ext(required=True)
+    y = ext.resample_poly_rows(
+        x.contiguous(), _i32(lens, x.device), _i32(out, x.device),
+        _resample_bank(d, x.device), d.L, d.M, d.H, max(out, default=0))
+    return y, torch.tensor(out, dtype=torch.long)
 
 
 # --------------------------------------------------------------------------- #

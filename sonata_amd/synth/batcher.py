@@ -18,8 +18,9 @@ import threading
 from concurrent.futures import Future
 from typing import List, Optional, Sequence
 
+from ..audio.resample import check_rate, is_identity, resample_poly
 from ..audio.samples import silence_samples
-from ..core import Audio, PcmAudio, SonataModel
+from ..core import Audio, AudioInfo, PcmAudio, SonataModel
 
 
 class DynamicBatcher:
@@ -29,7 +30,7 @@ class DynamicBatcher:
         self.max_batch = max_batch
         self.max_wait = max_wait_ms / 1000.0
         # items: (phonemes, future, prosody triple or None, pcm,
-        #         silence_ms or None)
+        #         silence_ms or None, output sample rate or None)
         self._q: "queue.Queue[Optional[tuple]]" = queue.Queue()
         self._worker = threading.Thread(target=self._run, daemon=True,
                                         name="sonata_batcher")
@@ -39,7 +40,8 @@ class DynamicBatcher:
     def submit(self, phonemes: str,
                prosody: Optional[Sequence[float]] = None,
                pcm: bool = False,
-               silence_ms: Optional[float] = None) -> "Future[Audio]":
+               silence_ms: Optional[float] = None,
+               sample_rate: Optional[int] = None) -> "Future[Audio]":
         """Queue one sentence; the future resolves with its Audio.
         `prosody`: optional (speed, volume, pitch) applied to this request's
         row by the model (speak_batch(prosody=...)); rows of one batch may
@@ -47,13 +49,24 @@ class DynamicBatcher:
         `pcm=True`: the future resolves with a PcmAudio (wire-format int16)
         with `silence_ms` of silence appended.  A bucket whose requests all
         want PCM runs one speak_batch_pcm; in a mixed bucket the PCM rows
-        are converted on the host.  The bytes are the same either way."""
+        are converted on the host.  The bytes are the same either way.
+        `sample_rate`: optional output rate of this request's row; it rides
+        with the request as the prosody triple does, and requests with
+        different rates still share one speak_batch* call.  A rate the
+        filter does not serve raises ValueError here."""
         if self._closed:
             raise RuntimeError("batcher closed")
         assert pcm or not silence_ms, "silence_ms rides with pcm requests"
+        if sample_rate is not None:
+            native = self.model.audio_output_info().sample_rate
+            if is_identity(native, sample_rate):
+                sample_rate = None
+            else:
+                check_rate(native, sample_rate)
+                sample_rate = int(sample_rate)
         f: "Future[Audio]" = Future()
         self._q.put((phonemes, f, tuple(prosody) if prosody is not None
-                     else None, bool(pcm), silence_ms))
+                     else None, bool(pcm), silence_ms, sample_rate))
         return f
 
     def synthesize(self, phonemes: str) -> Audio:
@@ -104,13 +117,23 @@ class DynamicBatcher:
         prosody = [it[2] for it in bucket]
         kw = {"prosody": prosody} if any(
             p is not None for p in prosody) else {}
+        rates = [it[5] for it in bucket]
+        host_rate = False
+        if any(r is not None for r in rates):
+            if getattr(self.model, "supports_output_rate", False):
+                kw["sample_rate"] = rates
+            else:
+                host_rate = True  # converted below, after the float batch
         try:
-            if all(it[3] for it in bucket) and getattr(
+            if all(it[3] for it in bucket) and not host_rate and getattr(
                     self.model, "supports_device_pcm", False):
                 audios = self.model.speak_batch_pcm(
                     phonemes, silence_ms=[it[4] for it in bucket], **kw)
             else:
                 audios = self.model.speak_batch(phonemes, **kw)
+                if host_rate:
+                    audios = [self._host_rate(a, r)
+                              for a, r in zip(audios, rates)]
                 audios = [self._host_pcm(a, it[4]) if it[3] else a
                           for it, a in zip(bucket, audios)]
             for it, audio in zip(bucket, audios):
@@ -119,6 +142,14 @@ class DynamicBatcher:
             for it in bucket:
                 if not it[1].done():
                     it[1].set_exception(e)
+
+    @staticmethod
+    def _host_rate(audio: Audio, rate: Optional[int]) -> Audio:
+        if rate is None:
+            return audio
+        return Audio(resample_poly(audio.samples, audio.info.sample_rate,
+                                   rate),
+                     AudioInfo(sample_rate=rate), audio.inference_ms)
 
     @staticmethod
     def _host_pcm(audio: Audio, silence_ms: Optional[float]) -> PcmAudio:

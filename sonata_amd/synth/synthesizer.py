@@ -24,6 +24,8 @@ from typing import Iterator, List, Optional
 import numpy as np
 
 from ..audio.prosody import apply_prosody
+from ..audio.resample import (StreamResampler, check_rate, is_identity,
+                              resample_poly)
 from ..audio.samples import generate_silence, merge, silence_samples
 from ..audio.wav import write_wav_file
 from ..core import Audio, AudioInfo, PcmAudio, SonataModel
@@ -70,12 +72,15 @@ def _percent(value: float, lo: float, hi: float) -> float:
 @dataclass
 class AudioOutputConfig:
     """Prosody knobs in percent (0-100) + appended silence, mirroring the
-    reference AudioOutputConfig (synth/src/lib.rs:28-117)."""
+    reference AudioOutputConfig (synth/src/lib.rs:28-117).  `sample_rate`
+    (Hz, not percent) asks for the result at another rate than the voice's
+    own; it is no part of `is_noop`, which speaks of prosody alone."""
 
     rate: Optional[float] = None
     volume: Optional[float] = None
     pitch: Optional[float] = None
     appended_silence_ms: Optional[float] = None
+    sample_rate: Optional[int] = None
 
     def prosody_triple(self):
         """(speed, volume, pitch) as parameters (not percent) — what `apply`
@@ -141,6 +146,26 @@ class SonataSpeechSynthesizer:
         return device_prosody_enabled(self.model) and cfg is not None \
             and not cfg.is_noop
 
+    def output_rate(self, cfg: Optional[AudioOutputConfig]) -> Optional[int]:
+        """The rate `cfg` asks for when it differs from the voice's own,
+        else None.  Raises ValueError for a rate the filter does not serve."""
+        if cfg is None or getattr(cfg, "sample_rate", None) is None:
+            return None
+        native = self.model.audio_output_info().sample_rate
+        if is_identity(native, cfg.sample_rate):
+            return None
+        check_rate(native, cfg.sample_rate)
+        return int(cfg.sample_rate)
+
+    def device_rate(self, cfg: Optional[AudioOutputConfig]) -> bool:
+        """True when the conversion to cfg's rate runs inside speak_batch*:
+        the model offers it and lives on cuda, and prosody, which comes
+        first, does not have to run on the host."""
+        dev = getattr(self.model, "device", None)
+        return (getattr(self.model, "supports_output_rate", False)
+                and getattr(dev, "type", None) == "cuda"
+                and (cfg.is_noop or self.device_prosody(cfg)))
+
     def _speak_device_prosody(self, sentences: List[str],
                               cfg: AudioOutputConfig) -> List[Audio]:
         """One speak_batch with cfg's prosody applied on the device; _post
@@ -150,13 +175,44 @@ class SonataSpeechSynthesizer:
             sentences, prosody=[triple] * len(sentences))
         return [self._post(a, cfg, prosody_done=True) for a in batch]
 
+    def _speak_rate(self, sentences: List[str], cfg: AudioOutputConfig,
+                    rate: int) -> List[Audio]:
+        """One batch at another output rate.  On the device: prosody and the
+        conversion inside speak_batch, silence here.  Else the float batch
+        is finished on the host: prosody, resample_poly, silence."""
+        if self.device_rate(cfg):
+            kw = {}
+            if not cfg.is_noop:
+                kw["prosody"] = [cfg.prosody_triple()] * len(sentences)
+            batch = self.model.speak_batch(sentences, sample_rate=rate, **kw)
+            return [self._post(a, cfg, prosody_done=True) for a in batch]
+        if self.device_prosody(cfg):
+            batch = self.model.speak_batch(
+                sentences, prosody=[cfg.prosody_triple()] * len(sentences))
+            return [self._post(a, cfg, prosody_done=True, rate=rate)
+                    for a in batch]
+        batch = self.model.speak_batch(sentences)
+        return [self._post(a, cfg, rate=rate) for a in batch]
+
+    @staticmethod
+    def _to_rate(audio: Audio, rate: Optional[int]) -> Audio:
+        if rate is None or audio.info.sample_rate == rate:
+            return audio
+        return Audio(resample_poly(audio.samples, audio.info.sample_rate, rate),
+                     AudioInfo(sample_rate=rate), audio.inference_ms)
+
     def _post(self, audio: Audio, cfg: Optional[AudioOutputConfig],
-              prosody_done: bool = False) -> Audio:
+              prosody_done: bool = False,
+              rate: Optional[int] = None) -> Audio:
         if cfg is None:
             return audio
         samples = audio.samples
         if not cfg.is_noop and not prosody_done:
             samples = cfg.apply(samples, audio.info.sample_rate)
+        if rate is not None:
+            audio = self._to_rate(
+                Audio(samples, audio.info, audio.inference_ms), rate)
+            samples = audio.samples
         if cfg.appended_silence_ms:
             samples = merge(
                 samples,
@@ -175,24 +231,43 @@ class SonataSpeechSynthesizer:
         has to run on the host keeps the float path up to the conversion."""
         host_prosody = (cfg is not None and not cfg.is_noop
                         and not self.device_prosody(cfg))
+        rate = self.output_rate(cfg)
+        if rate is not None and not self.device_rate(cfg):
+            # the conversion runs on the host, so the float path is kept up
+            # to it (device prosody first, where it is on)
+            if self.device_prosody(cfg):
+                batch = self.model.speak_batch(
+                    sentences,
+                    prosody=[cfg.prosody_triple()] * len(sentences))
+                return [self.to_pcm(a, cfg, prosody_done=True, rate=rate)
+                        for a in batch]
+            batch = self.model.speak_batch(sentences)
+            return [self.to_pcm(a, cfg, rate=rate) for a in batch]
         if getattr(self.model, "supports_device_pcm", False) \
                 and not host_prosody:
             triple = (cfg.prosody_triple()
                       if cfg is not None and not cfg.is_noop else None)
+            kw = {"sample_rate": rate} if rate is not None else {}
             return self.model.speak_batch_pcm(
                 sentences,
                 prosody=[triple] * len(sentences) if triple else None,
-                silence_ms=cfg.appended_silence_ms if cfg else None)
+                silence_ms=cfg.appended_silence_ms if cfg else None, **kw)
+        if rate is not None:
+            return [PcmAudio.from_audio(a)
+                    for a in self._speak_rate(sentences, cfg, rate)]
         batch = self.model.speak_batch(sentences)
         return [self.to_pcm(a, cfg) for a in batch]
 
     def to_pcm(self, audio: Audio, cfg: Optional[AudioOutputConfig],
-               prosody_done: bool = False) -> PcmAudio:
-        """Host finish of one float result: prosody unless done, then the
-        int16 conversion with cfg's silence appended."""
+               prosody_done: bool = False,
+               rate: Optional[int] = None) -> PcmAudio:
+        """Host finish of one float result: prosody unless done, the
+        conversion to `rate` when one is given, then the int16 conversion
+        with cfg's silence appended (counted at the result's rate)."""
         if cfg is not None and not cfg.is_noop and not prosody_done:
             audio = Audio(cfg.apply(audio.samples, audio.info.sample_rate),
                           audio.info, audio.inference_ms)
+        audio = self._to_rate(audio, rate)
         sil = (silence_samples(cfg.appended_silence_ms,
                                audio.info.sample_rate)
                if cfg is not None and cfg.appended_silence_ms else 0)
@@ -207,10 +282,14 @@ class SonataSpeechSynthesizer:
         (reference SonataSpeechStreamLazy, synth/src/lib.rs:282-307).
         `pcm=True` yields PcmAudio (int16, converted on the device when the
         model can) instead of float Audio; the wire bytes are the same."""
+        rate = self.output_rate(output_config)
         phonemes = self.model.phonemize_text(text)
         for sent in phonemes:
             if pcm:
                 yield self._speak_pcm([sent], output_config)[0]
+                continue
+            if rate is not None:
+                yield self._speak_rate([sent], output_config, rate)[0]
                 continue
             if self.device_prosody(output_config):
                 yield self._speak_device_prosody([sent], output_config)[0]
@@ -230,6 +309,9 @@ class SonataSpeechSynthesizer:
             return iter(())
         if pcm:
             return iter(self._speak_pcm(list(phonemes), output_config))
+        rate = self.output_rate(output_config)
+        if rate is not None:
+            return iter(self._speak_rate(list(phonemes), output_config, rate))
         if self.device_prosody(output_config):
             return iter(self._speak_device_prosody(list(phonemes),
                                                    output_config))
@@ -250,7 +332,12 @@ class SonataSpeechSynthesizer:
         With stream_prosody == "continuous" (and a model with batched
         streams) rate / pitch / volume run inside the model's stream path:
         a sentence's chunks concatenate to its one-shot prosody, nothing is
-        applied here and empty chunks are dropped."""
+        applied here and empty chunks are dropped.
+        An output sample rate is served by one audio.resample
+        StreamResampler per sentence, on the host, after prosody in either
+        mode: it is flushed at the end of the sentence, its empty chunks are
+        dropped and silence is counted at the output rate."""
+        rate = self.output_rate(output_config)
         phonemes = self.model.phonemize_text(text)
         info = self.model.audio_output_info()
         q: "queue.Queue" = queue.Queue()
@@ -295,17 +382,26 @@ class SonataSpeechSynthesizer:
                         )
                     else:
                         it = iter([self.model.speak_one_sentence(sent).samples])
+                    rs = (StreamResampler(info.sample_rate, rate)
+                          if rate is not None else None)
                     for chunk in it:
-                        if triple is not None:
-                            if len(chunk):
-                                q.put(chunk)
-                            continue
-                        if output_config is not None and not output_config.is_noop:
+                        if triple is None and output_config is not None \
+                                and not output_config.is_noop:
                             chunk = output_config.apply(chunk, info.sample_rate)
+                        if rs is not None:
+                            chunk = rs.push(chunk)
+                        if (triple is not None or rs is not None) \
+                                and not len(chunk):
+                            continue
                         q.put(chunk)
+                    if rs is not None:
+                        chunk = rs.flush()
+                        if len(chunk):
+                            q.put(chunk)
                     if output_config is not None and output_config.appended_silence_ms:
                         q.put(generate_silence(
-                            output_config.appended_silence_ms, info.sample_rate
+                            output_config.appended_silence_ms,
+                            rate if rate is not None else info.sample_rate
                         ))
                 q.put(DONE)
             except BaseException as e:  # propagate to consumer
@@ -333,6 +429,7 @@ class SonataSpeechSynthesizer:
         info = self.model.audio_output_info()
         inference_ms = 0.0
         for audio in self.synthesize_parallel(text, output_config):
+            info = audio.info  # the result's own rate
             pieces.append(audio.samples)
             inference_ms += audio.inference_ms
         samples = (
