@@ -74,6 +74,22 @@ torch::Tensor attn_relpos_cl(torch::Tensor qkv, torch::Tensor rel_k,
 torch::Tensor depthwise_cl(torch::Tensor x, torch::Tensor w,
                            c10::optional<torch::Tensor> bias, long dil,
                            long pad);
+torch::Tensor wn_step(torch::Tensor h, c10::optional<torch::Tensor> output,
+                      torch::Tensor rs, torch::Tensor mc, long layer);
+std::vector<torch::Tensor> flow_split_rev(torch::Tensor xc);
+torch::Tensor spline_tail(torch::Tensor inputs, torch::Tensor cumwidths,
+                          torch::Tensor cumheights, torch::Tensor derivatives,
+                          double tail_bound);
+std::vector<torch::Tensor> dds_sep_ln_gelu(
+    torch::Tensor x, c10::optional<torch::Tensor> g, torch::Tensor mc,
+    torch::Tensor w, torch::Tensor bias, torch::Tensor gamma,
+    torch::Tensor beta, long dil, double eps);
+torch::Tensor ln_gelu_add(torch::Tensor y, torch::Tensor t, torch::Tensor mc,
+                          torch::Tensor gamma, torch::Tensor beta,
+                          bool last, double eps);
+std::vector<torch::Tensor> coupling_tail(torch::Tensor x0, torch::Tensor x1,
+                                         torch::Tensor post, torch::Tensor mc,
+                                         bool last);
 
 namespace sonata {
 
@@ -82,6 +98,14 @@ namespace {
 constexpr double kLRelu = 0.1;
 
 long round_up(long v, long m) { return (v + m - 1) / m * m; }
+
+// SONATA_FUSED_FRONT=0 selects the eager ATen glue the fused front-end
+// kernels replace (bit-identical; kept so one build can test the equality).
+// Read per call, default on.
+bool fused_front() {
+  const char* e = getenv("SONATA_FUSED_FRONT");
+  return !(e && e[0] == '0');
+}
 
 std::string read_file(const std::string& path) {
   std::ifstream f(path, std::ios::binary);
@@ -368,11 +392,14 @@ torch::Tensor VitsEngine::gate(torch::Tensor x, c10::optional<torch::Tensor> g,
 }
 
 torch::Tensor VitsEngine::expand(torch::Tensor stats, torch::Tensor durs,
-                                 torch::Tensor y_lengths) const {
-  long F_max = y_lengths.max().item<long>();
+                                 torch::Tensor y_lengths, long F_max) const {
+  if (F_max < 0) F_max = y_lengths.max().item<long>();
   if (gpu()) {
     return expand_states(stats.contiguous(),
-                         durs.to(torch::kInt32).contiguous(), F_max);
+                         durs.scalar_type() == torch::kInt32
+                             ? durs.contiguous()
+                             : durs.to(torch::kInt32).contiguous(),
+                         F_max);
   }
   long B = stats.size(0), T = stats.size(2);
   auto out = torch::zeros({B, stats.size(1), F_max}, stats.options());
@@ -449,9 +476,16 @@ torch::Tensor VitsEngine::attention(torch::Tensor x, torch::Tensor attn_mask,
   return conv(out, mod + ".conv_o");
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor>
 VitsEngine::text_encoder(torch::Tensor ids, torch::Tensor lengths) const {
   if (gpu() && dtype_ == torch::kBFloat16) {
+    // LayerNorm parameters: the cached f32 copies when fused (row_ln_cl
+    // otherwise converts the bf16 constants on every call)
+    const bool fused = fused_front();
+    auto lnp = [&](const std::string& name) {
+      return fused ? bias_f32(name) : p(name);
+    };
     // channel-last encoder (mirrors vits.py TextEncoder._forward_cl):
     // the embedding is already [B,T,H]; attention heads are a free view;
     // FFN runs on cl MFMA convs with fused ReLU + ragged-row masking.
@@ -494,8 +528,8 @@ VitsEngine::text_encoder(torch::Tensor ids, torch::Tensor lengths) const {
                                  cfg_.window_size, scale);
       auto y = lin(outt, am + ".conv_o");
       x = row_ln_cl(x.contiguous(), y.contiguous(),
-                    p("enc_p.norm1." + li + ".gamma"),
-                    p("enc_p.norm1." + li + ".beta"), 1e-5);
+                    lnp("enc_p.norm1." + li + ".gamma"),
+                    lnp("enc_p.norm1." + li + ".beta"), 1e-5);
       std::string f1 = "enc_p.ffn_layers." + li + ".conv1";
       std::string f2 = "enc_p.ffn_layers." + li + ".conv2";
       long pad = cfg_.kernel_size / 2;
@@ -510,14 +544,23 @@ VitsEngine::text_encoder(torch::Tensor ids, torch::Tensor lengths) const {
                           bias_f32(f2 + ".bias"), wf2.size(0), wf2.size(2),
                           pad, 1, -1.0, 0, 0.0, c10::nullopt, lens32);
       x = row_ln_cl(x.contiguous(), f.contiguous(),
-                    p("enc_p.norm2." + li + ".gamma"),
-                    p("enc_p.norm2." + li + ".beta"), 1e-5);
+                    lnp("enc_p.norm2." + li + ".gamma"),
+                    lnp("enc_p.norm2." + li + ".beta"), 1e-5);
     }
     auto stats = (lin(x, "enc_p.proj") * mask_cl).transpose(1, 2);
-    auto chunks = stats.chunk(2, 1);
     auto x_mask = mask_cl.transpose(1, 2);
+    if (fused) {
+      // one [B,2C,T] copy; m_p and logs_p are views of it, and
+      // infer_encoder expands both halves in one launch
+      stats = stats.contiguous();
+      auto chunks = stats.chunk(2, 1);
+      return {(x.transpose(1, 2) * x_mask).contiguous(), chunks[0],
+              chunks[1], x_mask, stats};
+    }
+    auto chunks = stats.chunk(2, 1);
     return {(x.transpose(1, 2) * x_mask).contiguous(),
-            chunks[0].contiguous(), chunks[1].contiguous(), x_mask};
+            chunks[0].contiguous(), chunks[1].contiguous(), x_mask,
+            torch::Tensor()};
   }
   auto x = torch::embedding(p("enc_p.emb.weight"), ids) *
            std::sqrt((double)cfg_.hidden);
@@ -541,7 +584,7 @@ VitsEngine::text_encoder(torch::Tensor ids, torch::Tensor lengths) const {
   }
   auto stats = conv(x, "enc_p.proj") * x_mask;
   auto chunks = stats.chunk(2, 1);
-  return {x, chunks[0], chunks[1], x_mask};
+  return {x, chunks[0], chunks[1], x_mask, torch::Tensor()};
 }
 
 // ---------------------------------------------------------------------- //
@@ -591,6 +634,48 @@ torch::Tensor VitsEngine::flow_reverse(torch::Tensor x, torch::Tensor mask,
     auto xc = x.transpose(1, 2).contiguous();       // [B,F,C]
     auto mc = mask.transpose(1, 2).contiguous();    // [B,F,1]
     const long H = cfg_.hidden;
+    if (fused_front() && half % 8 == 0 && H % 8 == 0) {
+      // fused glue (csrc/elementwise.hip wn_step / coupling_tail): the
+      // same arithmetic and roundings as the loop below, without its
+      // per-op passes.  The state is the flipped (x0, x1) pair; no weight
+      // is reordered, the flips are index permutations in the kernels.
+      auto xs = flow_split_rev(xc);
+      auto x0 = xs[0], x1 = xs[1];
+      for (long f = 3; f >= 0; --f) {
+        std::string mod = "flow.flows." + std::to_string(f);
+        auto h = lin(x0, mod + ".pre") * mc;
+        torch::Tensor output;
+        c10::optional<torch::Tensor> g_all;
+        if (g.has_value() && has(mod + ".enc.cond_layer.weight"))
+          g_all = torch::linear(
+              g->squeeze(-1), p(mod + ".enc.cond_layer.weight").squeeze(-1),
+              p(mod + ".enc.cond_layer.bias"));
+        for (long i = 0; i < 4; ++i) {
+          std::string li = std::to_string(i);
+          auto cw = p(mod + ".enc.in_layers." + li + ".weight");
+          auto x_in = conv1d_cl_fused(
+              h, perm_conv(mod + ".enc.in_layers." + li + ".weight"),
+              bias_f32(mod + ".enc.in_layers." + li + ".bias"), cw.size(0),
+              cw.size(2), (cw.size(2) - 1) / 2, 1, -1.0, 0, 0.0,
+              c10::nullopt, c10::nullopt);
+          c10::optional<torch::Tensor> g_l;
+          if (g_all.has_value()) g_l = g_all->narrow(-1, i * 2 * H, 2 * H);
+          auto acts = fused_gate_cl(x_in, g_l, H);
+          auto res_skip = lin(acts, mod + ".enc.res_skip_layers." + li);
+          if (i == 0)
+            output = wn_step(h, c10::nullopt, res_skip, mc, 0);
+          else if (i < 3)
+            wn_step(h, output, res_skip, mc, 1);
+          else
+            h = wn_step(h, output, res_skip, mc, 2);
+        }
+        auto post = lin(h, mod + ".post");
+        auto nx = coupling_tail(x0, x1, post, mc, /*last=*/f == 0);
+        if (f == 0) return nx[0].transpose(1, 2).contiguous();
+        x0 = nx[0];
+        x1 = nx[1];
+      }
+    }
     for (long f = 3; f >= 0; --f) {
       xc = torch::flip(xc, {-1});
       std::string mod = "flow.flows." + std::to_string(f);
@@ -751,6 +836,86 @@ std::pair<torch::Tensor, torch::Tensor> rq_spline(
   return {outputs, logabsdet};
 }
 
+// Inverse spline as inference uses it: dense, sync-free, no logabsdet
+// (vits.py rational_quadratic_spline).  The spline is evaluated on every
+// element with tail-clamped inputs and blended with the identity tails by
+// where(); no boolean-mask compaction, so no host sync and no nonzero /
+// masked_select / index launches.  Per element the operations and their
+// order are rq_spline's, so an inside element gets the same bits.
+torch::Tensor rq_spline_inverse(torch::Tensor inputs, torch::Tensor uw,
+                                torch::Tensor uh, torch::Tensor ud,
+                                double tail_bound, bool tail_kernel) {
+  const double min_bin_width = 1e-3, min_bin_height = 1e-3,
+               min_derivative = 1e-3;
+  double constant = std::log(std::exp(1.0 - min_derivative) - 1.0);
+  ud = torch::constant_pad_nd(ud, {1, 1}, constant);
+  long num_bins = uw.size(-1);
+  if (tail_kernel) {
+    // softmax, cumsum and softplus stay ATen (their reduction order cannot
+    // be restated); everything after them is one HIP kernel that rounds as
+    // the ATen chain below does (csrc/elementwise.hip spline_tail)
+    TORCH_CHECK(inputs.is_cuda() && inputs.scalar_type() == torch::kBFloat16 &&
+                    num_bins == 10,
+                "rq_spline_inverse: the tail kernel is bf16, GPU, 10 bins");
+    auto cum = [&](torch::Tensor u, double min_bin) {
+      auto v = min_bin + (1 - min_bin * num_bins) * torch::softmax(u, -1);
+      return torch::cumsum(v, -1).contiguous();
+    };
+    auto derivatives = (min_derivative + torch::softplus(ud)).contiguous();
+    return spline_tail(inputs, cum(uw, min_bin_width),
+                       cum(uh, min_bin_height), derivatives, tail_bound);
+  }
+  auto inside = (inputs >= -tail_bound) & (inputs <= tail_bound);
+  auto x = torch::clamp(inputs, -tail_bound, tail_bound);
+
+  auto widths = torch::softmax(uw, -1);
+  widths = min_bin_width + (1 - min_bin_width * num_bins) * widths;
+  auto cumwidths = torch::cumsum(widths, -1);
+  cumwidths = torch::constant_pad_nd(cumwidths, {1, 0}, 0.0);
+  cumwidths = (2 * tail_bound) * cumwidths - tail_bound;
+  cumwidths.index_put_({torch::indexing::Ellipsis, 0}, -tail_bound);
+  cumwidths.index_put_({torch::indexing::Ellipsis, -1}, tail_bound);
+  widths = cumwidths.narrow(-1, 1, num_bins) -
+           cumwidths.narrow(-1, 0, num_bins);
+
+  auto derivatives = min_derivative + torch::softplus(ud);
+
+  auto heights = torch::softmax(uh, -1);
+  heights = min_bin_height + (1 - min_bin_height * num_bins) * heights;
+  auto cumheights = torch::cumsum(heights, -1);
+  cumheights = torch::constant_pad_nd(cumheights, {1, 0}, 0.0);
+  cumheights = (2 * tail_bound) * cumheights - tail_bound;
+  cumheights.index_put_({torch::indexing::Ellipsis, 0}, -tail_bound);
+  cumheights.index_put_({torch::indexing::Ellipsis, -1}, tail_bound);
+  heights = cumheights.narrow(-1, 1, num_bins) -
+            cumheights.narrow(-1, 0, num_bins);
+
+  // x clamped exactly onto +tail_bound lands one past the last bin
+  auto bin_idx = (torch::sum(x.unsqueeze(-1) >= cumheights, -1) - 1)
+                     .unsqueeze(-1)
+                     .clamp(0, num_bins - 1);
+  auto g1 = [&](torch::Tensor t) {
+    return t.gather(-1, bin_idx).squeeze(-1);
+  };
+  auto in_cumwidths = g1(cumwidths);
+  auto in_widths = g1(widths);
+  auto in_cumheights = g1(cumheights);
+  auto in_heights = g1(heights);
+  auto delta = in_heights / in_widths;
+  auto in_deriv = g1(derivatives);
+  auto in_deriv_p1 = g1(derivatives.narrow(-1, 1, derivatives.size(-1) - 1));
+
+  auto a = (x - in_cumheights) * (in_deriv + in_deriv_p1 - 2 * delta) +
+           in_heights * (delta - in_deriv);
+  auto bq = in_heights * in_deriv -
+            (x - in_cumheights) * (in_deriv + in_deriv_p1 - 2 * delta);
+  auto c = -delta * (x - in_cumheights);
+  auto disc = (bq.pow(2) - 4 * a * c).clamp_min(0.0);
+  auto root = (2 * c) / (-bq - torch::sqrt(disc));
+  auto out = root * in_widths + in_cumwidths;
+  return torch::where(inside, out, inputs);
+}
+
 torch::Tensor VitsEngine::dds_conv(torch::Tensor x, torch::Tensor mask,
                                    c10::optional<torch::Tensor> g,
                                    const std::string& mod, long n_layers,
@@ -785,9 +950,37 @@ torch::Tensor VitsEngine::sdp_infer(torch::Tensor x, torch::Tensor mask,
       return torch::linear(t, p(mod + ".weight").squeeze(-1),
                            p(mod + ".bias"));
     };
+    const bool fused = fused_front();
+    auto lnp = [&](const std::string& name) {
+      return fused ? bias_f32(name) : p(name);
+    };
     auto dds_cl = [&](torch::Tensor t, torch::Tensor mc,
                       c10::optional<torch::Tensor> gc,
                       const std::string& mod) {
+      if (fused && t.size(-1) <= 512) {
+        // fused DDS layer (csrc/elementwise.hip): twelve launches become
+        // three, same arithmetic and roundings as the loop below
+        t = t.contiguous();
+        for (long i = 0; i < 3; ++i) {
+          std::string li = std::to_string(i);
+          long dilation = 1;
+          for (long j = 0; j < i; ++j) dilation *= 3;
+          c10::optional<torch::Tensor> g0;
+          if (i == 0 && gc.has_value()) g0 = gc->contiguous();
+          auto r = dds_sep_ln_gelu(
+              t, g0, mc, p(mod + ".convs_sep." + li + ".weight"),
+              bias_f32(mod + ".convs_sep." + li + ".bias"),
+              bias_f32(mod + ".norms_1." + li + ".gamma"),
+              bias_f32(mod + ".norms_1." + li + ".beta"), dilation, 1e-5);
+          if (g0.has_value()) t = r[1];
+          auto y = lin(r[0], mod + ".convs_1x1." + li);
+          t = ln_gelu_add(y.contiguous(), t, mc,
+                          bias_f32(mod + ".norms_2." + li + ".gamma"),
+                          bias_f32(mod + ".norms_2." + li + ".beta"),
+                          /*last=*/i == 2, 1e-5);
+        }
+        return t;
+      }
       if (gc.has_value()) t = t + *gc;
       const long C = t.size(-1);
       for (long i = 0; i < 3; ++i) {
@@ -800,13 +993,13 @@ torch::Tensor VitsEngine::sdp_infer(torch::Tensor x, torch::Tensor mask,
                               bias_f32(mod + ".convs_sep." + li + ".bias"),
                               dilation, pad);
         y = row_ln_cl(y.contiguous(), c10::nullopt,
-                      p(mod + ".norms_1." + li + ".gamma"),
-                              p(mod + ".norms_1." + li + ".beta"), 1e-5);
+                      lnp(mod + ".norms_1." + li + ".gamma"),
+                      lnp(mod + ".norms_1." + li + ".beta"), 1e-5);
         y = torch::gelu(y);
         y = lin(y, mod + ".convs_1x1." + li);
         y = row_ln_cl(y.contiguous(), c10::nullopt,
-                      p(mod + ".norms_2." + li + ".gamma"),
-                              p(mod + ".norms_2." + li + ".beta"), 1e-5);
+                      lnp(mod + ".norms_2." + li + ".gamma"),
+                      lnp(mod + ".norms_2." + li + ".beta"), 1e-5);
         y = torch::gelu(y);
         t = t + y;
       }
@@ -841,8 +1034,9 @@ torch::Tensor VitsEngine::sdp_infer(torch::Tensor x, torch::Tensor mask,
       auto ud = h4.index({torch::indexing::Ellipsis,
                           torch::indexing::Slice(2 * num_bins,
                                                  torch::indexing::None)});
-      auto res = rq_spline(z1, uw, uh, ud, true, 5.0);
-      return torch::cat({z0, res.first}, 1) * mask;
+      auto z1n = fused ? rq_spline_inverse(z1, uw, uh, ud, 5.0, true)
+                       : rq_spline(z1, uw, uh, ud, true, 5.0).first;
+      return torch::cat({z0, z1n}, 1) * mask;
     };
     auto flip = [&](torch::Tensor t) { return torch::flip(t, {1}); };
     z = flip(z);
@@ -891,8 +1085,9 @@ torch::Tensor VitsEngine::sdp_infer(torch::Tensor x, torch::Tensor mask,
     auto ud = h.index({torch::indexing::Ellipsis,
                        torch::indexing::Slice(2 * num_bins,
                                               torch::indexing::None)});
-    auto res = rq_spline(z1, uw, uh, ud, /*inverse=*/true, 5.0);
-    z1 = res.first;
+    z1 = fused_front()
+             ? rq_spline_inverse(z1, uw, uh, ud, 5.0, false)
+             : rq_spline(z1, uw, uh, ud, /*inverse=*/true, 5.0).first;
     return torch::cat({z0, z1}, 1) * mask;
   };
   // python module list: flows = [EWA(0), CF(1), Flip, CF(2), Flip, CF(3),
@@ -1087,17 +1282,26 @@ torch::Tensor VitsEngine::generator(torch::Tensor x,
 // ---------------------------------------------------------------------- //
 torch::Tensor VitsEngine::masked_noise(long B, long C, long T_max,
                                        torch::Tensor lengths,
-                                       std::vector<torch::Generator>& gens)
+                                       std::vector<torch::Generator>& gens,
+                                       torch::Tensor* seeds_dev)
     const {
   if (gpu()) {
     // ONE launch: counter-based normal noise keyed by (seed, c, t) —
     // replaces B per-row torch::randn launches + B .item() host syncs
     // per noise tensor (csrc/elementwise.hip seeded_noise_kernel; the
     // Python GPU path uses the same kernel, so engine == python holds)
-    std::vector<long> sv;
-    for (auto& g : gens) sv.push_back((long)g.current_seed());
-    auto seeds = torch::from_blob(sv.data(), {(long)sv.size()},
-                                  torch::kLong).clone().to(device_);
+    // seeds_dev: the caller's per-step copy of the seeds on the device,
+    // uploaded by the first noise tensor of the step and reused by the next
+    torch::Tensor seeds;
+    if (seeds_dev && seeds_dev->defined()) {
+      seeds = *seeds_dev;
+    } else {
+      std::vector<long> sv;
+      for (auto& g : gens) sv.push_back((long)g.current_seed());
+      seeds = torch::from_blob(sv.data(), {(long)sv.size()}, torch::kLong)
+                  .clone().to(device_);
+      if (seeds_dev) *seeds_dev = seeds;
+    }
     auto lens32 = lengths.to(device_).to(torch::kInt);
     return seeded_noise(B, C, T_max, lens32.contiguous(),
                         seeds.contiguous(),
@@ -1134,7 +1338,7 @@ VitsEngine::infer_encoder(torch::Tensor ids, torch::Tensor lengths,
     gens.push_back(g);
   }
 
-  auto [x, m_p, logs_p, x_mask] = text_encoder(ids, lengths);
+  auto [x, m_p, logs_p, x_mask, stats] = text_encoder(ids, lengths);
   c10::optional<torch::Tensor> g;
   if (has("emb_g.weight")) {
     torch::Tensor s = sid.has_value()
@@ -1144,7 +1348,10 @@ VitsEngine::infer_encoder(torch::Tensor ids, torch::Tensor lengths,
                                                   .device(device_));
     g = torch::embedding(p("emb_g.weight"), s).unsqueeze(-1);
   }
-  auto sdp_noise = masked_noise(B, 2, ids.size(1), lengths, gens);
+  // fused front end: the seeds go to the device once per step
+  torch::Tensor seeds_dev;
+  torch::Tensor* seeds_once = fused_front() ? &seeds_dev : nullptr;
+  auto sdp_noise = masked_noise(B, 2, ids.size(1), lengths, gens, seeds_once);
   auto logw = sdp_infer(x, x_mask, g, noise_w, sdp_noise);
   auto w = torch::exp(logw) * x_mask * length_scale;
   auto w_ceil = torch::ceil(w);
@@ -1152,15 +1359,32 @@ VitsEngine::infer_encoder(torch::Tensor ids, torch::Tensor lengths,
       torch::clamp_min(torch::sum(w_ceil, {1, 2}), 1).to(torch::kLong);
   long F_max = y_lengths.max().item<long>();
   auto y_mask = sequence_mask(y_lengths, F_max).to(x.dtype());
-  auto durations = w_ceil.squeeze(1).to(torch::kLong);
-  auto m_p_f = expand(m_p, durations, y_lengths);
-  auto logs_p_f = expand(logs_p, durations, y_lengths);
+  torch::Tensor m_p_f, logs_p_f;
+  if (stats.defined()) {
+    // fused front end: one int32 durs, the F_max already on the host, and
+    // one expand over the [B,2C,T] stats m_p and logs_p are the halves of
+    auto durs32 = w_ceil.squeeze(1).to(torch::kInt32);
+    const long C = m_p.size(1);
+    auto ef = expand(stats, durs32, y_lengths, F_max);
+    m_p_f = ef.narrow(1, 0, C);
+    logs_p_f = ef.narrow(1, C, C);
+  } else {
+    auto durations = w_ceil.squeeze(1).to(torch::kLong);
+    m_p_f = expand(m_p, durations, y_lengths);
+    logs_p_f = expand(logs_p, durations, y_lengths);
+  }
   auto pnoise = masked_noise(B, m_p_f.size(1), m_p_f.size(2), y_lengths,
-                             gens);
+                             gens, seeds_once);
   torch::Tensor z_p;
   if (gpu()) {
-    z_p = prior_sample(m_p_f.contiguous(), logs_p_f.contiguous(),
-                       y_mask.contiguous(), pnoise, noise_scale);
+    // the fused front end hands over views of one expanded tensor;
+    // prior_sample takes their batch stride, so nothing is copied
+    if (!stats.defined()) {
+      m_p_f = m_p_f.contiguous();
+      logs_p_f = logs_p_f.contiguous();
+    }
+    z_p = prior_sample(m_p_f, logs_p_f, y_mask.contiguous(), pnoise,
+                       noise_scale);
   } else {
     z_p = (m_p_f + pnoise * torch::exp(logs_p_f) * noise_scale) * y_mask;
   }

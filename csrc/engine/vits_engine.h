@@ -101,11 +101,15 @@ class VitsEngine {
                            c10::optional<torch::Tensor> residual = {}) const;
   torch::Tensor gate(torch::Tensor x, c10::optional<torch::Tensor> g,
                      long n_ch) const;
+  // F_max < 0: read y_lengths.max() back from the device
   torch::Tensor expand(torch::Tensor stats, torch::Tensor durs,
-                       torch::Tensor y_lengths) const;
+                       torch::Tensor y_lengths, long F_max = -1) const;
 
   // graph stages
-  std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+  // (x, m_p, logs_p, x_mask, stats): stats is the contiguous [B,2C,T]
+  // tensor m_p and logs_p are views of, defined on the fused front end only
+  std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+             torch::Tensor>
   text_encoder(torch::Tensor ids, torch::Tensor lengths) const;
   torch::Tensor attention(torch::Tensor x, torch::Tensor attn_mask,
                           const std::string& mod) const;
@@ -127,12 +131,21 @@ class VitsEngine {
 
   torch::Tensor masked_noise(long B, long C, long T_max,
                              torch::Tensor lengths,
-                             std::vector<torch::Generator>& gens) const;
+                             std::vector<torch::Generator>& gens,
+                             torch::Tensor* seeds_dev = nullptr) const;
 };
 
 // rational-quadratic spline (Durkan et al.), exposed for tests
 std::pair<torch::Tensor, torch::Tensor> rq_spline(
     torch::Tensor inputs, torch::Tensor uw, torch::Tensor uh,
     torch::Tensor ud, bool inverse, double tail_bound);
+
+// the inverse alone in the dense, sync-free form inference runs (no
+// boolean-mask compaction, no logabsdet); same per-element operations.
+// tail_kernel (bf16 on the GPU, 10 bins): everything after the softmax,
+// cumsum and softplus runs in one HIP kernel, bit-identical to the ATen tail
+torch::Tensor rq_spline_inverse(torch::Tensor inputs, torch::Tensor uw,
+                                torch::Tensor uh, torch::Tensor ud,
+                                double tail_bound, bool tail_kernel = false);
 
 }  // namespace sonata

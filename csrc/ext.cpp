@@ -25,6 +25,22 @@ torch::Tensor row_ln_cl(torch::Tensor x, c10::optional<torch::Tensor> resid,
 torch::Tensor depthwise_cl(torch::Tensor x, torch::Tensor w,
                            c10::optional<torch::Tensor> bias, long dil,
                            long pad);
+torch::Tensor wn_step(torch::Tensor h, c10::optional<torch::Tensor> output,
+                      torch::Tensor rs, torch::Tensor mc, long layer);
+std::vector<torch::Tensor> flow_split_rev(torch::Tensor xc);
+std::vector<torch::Tensor> coupling_tail(torch::Tensor x0, torch::Tensor x1,
+                                         torch::Tensor post, torch::Tensor mc,
+                                         bool last);
+std::vector<torch::Tensor> dds_sep_ln_gelu(
+    torch::Tensor x, c10::optional<torch::Tensor> g, torch::Tensor mc,
+    torch::Tensor w, torch::Tensor bias, torch::Tensor gamma,
+    torch::Tensor beta, long dil, double eps);
+torch::Tensor ln_gelu_add(torch::Tensor y, torch::Tensor t, torch::Tensor mc,
+                          torch::Tensor gamma, torch::Tensor beta,
+                          bool last, double eps);
+torch::Tensor spline_tail(torch::Tensor inputs, torch::Tensor cumwidths,
+                          torch::Tensor cumheights, torch::Tensor derivatives,
+                          double tail_bound);
 // conv1d.hip
 torch::Tensor conv1d_fused(torch::Tensor x, torch::Tensor w_perm,
                            c10::optional<torch::Tensor> bias, long Cout,
@@ -146,6 +162,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("row_ln_cl", &row_ln_cl,
         "LayerNorm over channel-last rows with fused residual add");
   m.def("depthwise_cl", &depthwise_cl, "channel-last depthwise conv1d");
+  m.def("wn_step", &wn_step,
+        "flow WaveNet residual/skip update in place (layer 0 first, 1 "
+        "middle, 2 last); returns output",
+        py::arg("h"), py::arg("output"), py::arg("rs"), py::arg("mc"),
+        py::arg("layer"));
+  m.def("flow_split_rev", &flow_split_rev,
+        "xc [B,F,C] -> the (x0, x1) halves of flip(xc, -1)");
+  m.def("coupling_tail", &coupling_tail,
+        "coupling-flow tail fused with the next flow's flip; last: "
+        "[cat(x0, x1_new)]",
+        py::arg("x0"), py::arg("x1"), py::arg("post"), py::arg("mc"),
+        py::arg("last"));
+  m.def("dds_sep_ln_gelu", &dds_sep_ln_gelu,
+        "DDS layer head: (x [+ g])*m -> depthwise k3 -> LN -> GELU; "
+        "returns [y] or, with g, [y, x + g]",
+        py::arg("x"), py::arg("g"), py::arg("mc"), py::arg("w"),
+        py::arg("bias"), py::arg("gamma"), py::arg("beta"), py::arg("dil"),
+        py::arg("eps") = 1e-5);
+  m.def("ln_gelu_add", &ln_gelu_add,
+        "DDS layer tail: t + GELU(LN(y)), times the mask when last",
+        py::arg("y"), py::arg("t"), py::arg("mc"), py::arg("gamma"),
+        py::arg("beta"), py::arg("last"), py::arg("eps") = 1e-5);
+  m.def("rq_spline_inverse", &sonata::rq_spline_inverse,
+        "dense, sync-free inverse rational-quadratic spline (no logabsdet); "
+        "tail_kernel: the part after softmax/cumsum/softplus as one kernel",
+        py::arg("inputs"), py::arg("uw"), py::arg("uh"), py::arg("ud"),
+        py::arg("tail_bound") = 5.0, py::arg("tail_kernel") = false);
+  m.def("spline_tail", &spline_tail,
+        "per-element tail of the inverse spline on cumsum'd widths/heights "
+        "and softplus'd derivatives",
+        py::arg("inputs"), py::arg("cumwidths"), py::arg("cumheights"),
+        py::arg("derivatives"), py::arg("tail_bound") = 5.0);
   m.def("conv1d_fused", &conv1d_fused, "MFMA conv1d with fused activations");
   m.def("convtranspose1d_fused", &convtranspose1d_fused,
         "MFMA transposed conv1d (phase-decomposed GEMMs)");

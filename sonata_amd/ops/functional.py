@@ -598,6 +598,67 @@ def row_ln_cl(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
 
 
 # --------------------------------------------------------------------------- #
+# fused glue of the engine's channel-last flow (csrc/elementwise.hip); bf16,
+# GPU only.  Each is bit-identical to the eager chain it replaces; the
+# engine (csrc/engine/vits_engine.cpp) is their caller, these wrappers exist
+# so tests can reach the kernels.
+# --------------------------------------------------------------------------- #
+def wn_step(h: torch.Tensor, output: Optional[torch.Tensor],
+            res_skip: torch.Tensor, mc: torch.Tensor, layer: int):
+    """One WaveNet layer's residual/skip update IN PLACE on h and output
+    ([B,F,H]); res_skip [B,F,2H] (layer 0 first / 1 middle) or [B,F,H]
+    (layer 2 last); mc [B,F,1].  Returns output: freshly allocated for
+    layer 0; for layer 2 it holds the masked result (the new h)."""
+    return hip_ext(required=True).wn_step(h, output, res_skip, mc, layer)
+
+
+def flow_split_rev(xc: torch.Tensor):
+    """xc [B,F,C] -> the contiguous (x0, x1) halves of flip(xc, -1)."""
+    x0, x1 = hip_ext(required=True).flow_split_rev(xc)
+    return x0, x1
+
+
+def coupling_tail(x0: torch.Tensor, x1: torch.Tensor, post: torch.Tensor,
+                  mc: torch.Tensor, last: bool):
+    """m = post*mc, x1 = (x1 - m)*mc, then either the next flow's flipped
+    (x0, x1) pair (last=False) or cat(x0, x1) as one [B,F,C] (last=True)."""
+    r = hip_ext(required=True).coupling_tail(x0, x1, post, mc, last)
+    return r[0] if last else (r[0], r[1])
+
+
+def dds_sep_ln_gelu(x: torch.Tensor, g: Optional[torch.Tensor],
+                    mc: torch.Tensor, weight: torch.Tensor,
+                    bias: torch.Tensor, gamma: torch.Tensor,
+                    beta: torch.Tensor, dilation: int, eps: float = 1e-5):
+    """DDS layer head on channel-last rows: t = x (+ g);
+    y = gelu(LN(depthwise_k3(t*mc))).  weight [C,1,3] bf16; bias, gamma, beta
+    f32 [C].  Returns (y, t); t is x itself without g."""
+    r = hip_ext(required=True).dds_sep_ln_gelu(x, g, mc, weight, bias, gamma,
+                                               beta, dilation, eps)
+    return (r[0], r[1]) if g is not None else (r[0], x)
+
+
+def ln_gelu_add(y: torch.Tensor, t: torch.Tensor, mc: torch.Tensor,
+                gamma: torch.Tensor, beta: torch.Tensor, last: bool,
+                eps: float = 1e-5) -> torch.Tensor:
+    """DDS layer tail: t + gelu(LN(y)), times mc when last."""
+    return hip_ext(required=True).ln_gelu_add(y, t, mc, gamma, beta, last,
+                                              eps)
+
+
+def rq_spline_inverse(inputs: torch.Tensor, uw: torch.Tensor,
+                      uh: torch.Tensor, ud: torch.Tensor,
+                      tail_bound: float = 5.0,
+                      tail_kernel: bool = False) -> torch.Tensor:
+    """The engine's dense, sync-free inverse rational-quadratic spline (no
+    logabsdet): ATen ops on either device, or with tail_kernel (bf16, GPU,
+    10 bins) one HIP kernel for everything after the softmax, cumsum and
+    softplus."""
+    return hip_ext(required=True).rq_spline_inverse(inputs, uw, uh, ud,
+                                                    tail_bound, tail_kernel)
+
+
+# --------------------------------------------------------------------------- #
 # batched prosody: rate / pitch / volume on [B, N] f32 rows with per-row
 # parameters (csrc/prosody.hip).  The CPU path calls the NumPy functions of
 # audio.prosody row by row and is the oracle; every length on both paths
