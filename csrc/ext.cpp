@@ -127,6 +127,11 @@ long pcm_tile();
 torch::Tensor resample_poly_rows(torch::Tensor x, torch::Tensor in_len,
                                  torch::Tensor out_len, torch::Tensor bank,
                                  long L, long M, long H, long n_out);
+torch::Tensor resample_poly_stream_rows(torch::Tensor x,
+                                        std::vector<int64_t> par,
+                                        torch::Tensor state,
+                                        torch::Tensor bank, long L, long M,
+                                        long H, long n_out);
 long resample_tile();
 // stream.hip
 torch::Tensor gather_windows(std::vector<torch::Tensor> zs,
@@ -247,6 +252,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-row polyphase FIR sample-rate conversion of [B,N] f32/bf16 by "
         "L/M; bank is the [K][L] f32 filter; returns y [B,n_out] f32",
         py::arg("x"), py::arg("in_len"), py::arg("out_len"), py::arg("bank"),
+        py::arg("L"), py::arg("M"), py::arg("H"), py::arg("n_out"));
+  m.def("resample_poly_stream_rows", &resample_poly_stream_rows,
+        "one round of per-row streaming polyphase FIR conversion on carry "
+        "++ chunk; state f32 [S,2,Kc] is ping-pong (reads buffer parity, "
+        "writes the other); returns y [R,n_out] f32",
+        py::arg("x"), py::arg("par"), py::arg("state"), py::arg("bank"),
         py::arg("L"), py::arg("M"), py::arg("H"), py::arg("n_out"));
   m.attr("RESAMPLE_TILE") = resample_tile();
   m.def("gather_windows", &gather_windows,

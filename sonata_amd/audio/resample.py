@@ -16,7 +16,10 @@ Polyphase form: K = ceil((2H+1)/L) taps per phase, bank[p][k] = h[p + k*L]
 which is zero phase: there is no delay to trim.  `resample_poly` (float64
 accumulation of the float32 bank, rounded to float32 once) is the semantic
 reference and the CPU path; `StreamResampler` is its chunked form and its
-chunks concatenate to the one-shot result.
+chunks concatenate to the one-shot result.  `PolyStreamPlan` / `PolyStream`
+are the chunked form for a stream whose total length is known up front: the
+plan fixes every length of every push on the host, which is what the device
+kernel for batched realtime streams runs on (see the end of this file).
 """
 
 from __future__ import annotations
@@ -178,3 +181,124 @@ class StreamResampler:
         if d is None:
             return np.zeros(0, dtype=np.float32)
         return self._emit(max(-(-self._seen * d.L // d.M), self._done))
+
+
+# --------------------------------------------------------------------------- #
+# Plan-driven streaming, for a stream whose total input length n is known up
+# front (a realtime stream's frames * hop): every length of every push is
+# host arithmetic, so the device kernel (csrc/resample.hip,
+# resample_poly_stream_rows) needs no sync and no flush round.
+#
+# After A input samples, output m is ready once x[j(m)] has arrived (j(m) <
+# A), so a push emits [done, e1) with
+#     e1 = max(min(max(ceil((A*L - H)/M), 0), n_out), done),
+# and the last push emits up to n_out = ceil(n*L/M): input past n is zero.
+# The next output reads from j(e1) - (K-1) on, so the logical input [keep, A)
+# with keep = clamp(j(e1) - (K-1), previous keep, A) is carried over.  j(e1)
+# >= A whenever e1 < n_out, and j(n_out) >= n, so the carry never exceeds
+# K - 1 samples (and reaches it).
+# --------------------------------------------------------------------------- #
+class PolyPush(NamedTuple):
+    """One push of a PolyStreamPlan, in global positions: the chunk is input
+    [a0, a0 + m), the carry read is input [carry_pos, carry_pos + carry_len)
+    (carry_pos + carry_len == a0), outputs [e0, e1) are emitted and input
+    [keep_pos, keep_pos + keep_len) (ending at a0 + m) is the new carry.
+    `parity` names the state buffer that holds the carry read; the new one
+    goes to buffer 1 - parity."""
+
+    n: int
+    n_out: int
+    a0: int
+    m: int
+    carry_pos: int
+    carry_len: int
+    e0: int
+    e1: int
+    keep_pos: int
+    keep_len: int
+    parity: int
+
+
+class PolyStreamPlan:
+    """The lengths of chunked resample_poly for a stream of `n` input
+    samples in all.  push(m, last) advances by one chunk of m samples."""
+
+    def __init__(self, n: int, rate_in: int, rate_out: int):
+        assert not is_identity(rate_in, rate_out), "identity needs no plan"
+        self.d = design(rate_in, rate_out)
+        self.n = int(n)
+        assert self.n >= 0
+        self.n_out = -(-self.n * self.d.L // self.d.M)
+        self.seen = 0  # input samples pushed (A)
+        self.done = 0  # output samples emitted
+        self.keep = 0  # the carry is input [keep, seen)
+        self.parity = 0  # flips on every push
+        self.closed = False
+
+    @property
+    def carry_cap(self) -> int:
+        return self.d.K - 1
+
+    def _j(self, m: int) -> int:
+        return (m * self.d.M + self.d.H) // self.d.L
+
+    def push(self, m: int, last: bool = False) -> PolyPush:
+        d = self.d
+        m = int(m)
+        assert m >= 0 and not self.closed, "push after the last chunk"
+        a0 = self.seen
+        A = a0 + m
+        assert A <= self.n, "more input than the plan was opened for"
+        e0 = self.done
+        if last:
+            assert A == self.n, "the chunk lengths must sum to n at last"
+            e1 = self.n_out
+            self.closed = True
+        else:
+            ready = max(-(-(A * d.L - d.H) // d.M), 0)
+            e1 = max(min(ready, self.n_out), e0)
+        carry_pos, carry_len = self.keep, a0 - self.keep
+        keep = min(max(self._j(e1) - (d.K - 1), self.keep), A)
+        keep_len = A - keep
+        assert 0 <= carry_len <= d.K - 1 and 0 <= keep_len <= d.K - 1, \
+            "carry above K - 1"
+        if e1 > e0:
+            # every index the emitted outputs read lies in carry ++ chunk,
+            # or outside [0, n)
+            lo = max(self._j(e0) - (d.K - 1), 0)
+            hi = min(self._j(e1 - 1), self.n - 1)
+            assert hi < lo or (lo >= carry_pos and hi < A), \
+                "an emitted output reads outside carry ++ chunk"
+        parity = self.parity
+        self.seen, self.done, self.keep = A, e1, keep
+        self.parity ^= 1
+        return PolyPush(self.n, self.n_out, a0, m, carry_pos, carry_len, e0,
+                        e1, keep, keep_len, parity)
+
+
+class PolyStream:
+    """A PolyStreamPlan plus, for the CPU path, the carry as a NumPy array:
+    push(chunk, last) returns float32 outputs (possibly none) that
+    concatenate to resample_poly of the whole input, bit for bit.  The
+    device path (ops.resample_poly_stream_rows) pushes the plan alone and
+    keeps the carry in an ops.PolyStreamState."""
+
+    def __init__(self, n: int, rate_in: int, rate_out: int):
+        self.plan = PolyStreamPlan(n, rate_in, rate_out)
+        self.rate_in = self.plan.d.rate_in
+        self.rate_out = self.plan.d.rate_out
+        self._carry = np.zeros(0, dtype=np.float64)
+
+    @property
+    def n_out(self) -> int:
+        return self.plan.n_out
+
+    def push(self, chunk, last: bool = False) -> np.ndarray:
+        chunk = np.asarray(chunk, dtype=np.float32).reshape(-1)
+        p = self.plan.push(len(chunk), last)
+        assert len(self._carry) == p.carry_len
+        buf = np.concatenate([self._carry, chunk.astype(np.float64)])
+        y = _outputs(self.plan.d, buf, p.carry_pos, p.e0, p.e1)
+        self._carry = buf[p.keep_pos - p.carry_pos :]
+        assert len(self._carry) == p.keep_len
+        return y.astype(np.float32)

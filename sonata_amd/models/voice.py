@@ -85,6 +85,8 @@ class VitsVoice(SonataModel):
         # device state of continuous stream prosody (ops.ProsodyStreamState),
         # indexed by tail slot; allocated with the first stream that asks
         self._prosody_state = None
+        # ops.PolyStreamState per output sample rate streams were opened at
+        self._poly_states: Dict[int, object] = {}
         self._tashkeel = None
         if config.espeak_voice.startswith("ar"):
             from ..text.tashkeel import TashkeelModel
@@ -579,8 +581,8 @@ class VitsVoice(SonataModel):
     # ------------------------------------------------------------------ #
     @torch.no_grad()
     def stream_open(self, phonemes_batch: Sequence[str], chunk_size=45,
-                    chunk_padding: int = 3,
-                    prosody=None) -> List["StreamState"]:
+                    chunk_padding: int = 3, prosody=None,
+                    sample_rate=None) -> List["StreamState"]:
         """Encode a list of sentences in ONE batched encoder call and return
         one StreamState per sentence, to be advanced by stream_round.
         `chunk_size` is an int or one int per sentence.  Speaker and scales
@@ -591,8 +593,17 @@ class VitsVoice(SonataModel):
         stream with a triple emits, over all its chunks, what
         ops.apply_prosody_rows gives on its whole plain audio (frames * hop
         samples, known here): the stretcher's state stays on the device
-        between rounds, and a round may emit an empty chunk."""
+        between rounds, and a round may emit an empty chunk.
+        `sample_rate`: one output rate, or one rate or None per sentence
+        (checked as speak_batch's).  A stream with a rate emits, over all
+        its chunks, what ops.resample_rows gives on its whole audio (after
+        prosody): the filter's carry stays on the device between rounds
+        (ops.resample_poly_stream_rows), and a round may emit an empty
+        chunk."""
         B = len(phonemes_batch)
+        native = self.config.sample_rate
+        rates = [None if r == native else r
+                 for r in self._row_rates(sample_rate, B)]
         if prosody is None:
             prosody = [None] * B
         assert len(prosody) == B, "one prosody triple (or None) per sentence"
@@ -634,19 +645,40 @@ class VitsVoice(SonataModel):
             slots = self._tail_slots_take(B)
             if any(t is not None for t in prosody):
                 self._prosody_reserve()
+            self._poly_reserve(rates)
         from ..audio.prosody import StreamProsody
+        from ..audio.resample import PolyStream
 
         hop = self.net.arch.hop_length
-        return [
-            StreamState(
+        states = []
+        for b in range(B):
+            pros = None if prosody[b] is None else StreamProsody(
+                int(frames[b]) * hop, native, *prosody[b])
+            # the resampler's input length: what the stages before it emit
+            n_in = int(frames[b]) * hop if pros is None else pros.n_out
+            states.append(StreamState(
                 index=b, z=z, row=b, frames=int(frames[b]),
                 g=g[b : b + 1] if g is not None else None,
                 plan=chunk_plan(int(frames[b]), chunk_size[b], chunk_padding),
-                slot=slots[b],
-                prosody=None if prosody[b] is None else StreamProsody(
-                    int(frames[b]) * hop, self.config.sample_rate,
-                    *prosody[b]))
-            for b in range(B)]
+                slot=slots[b], prosody=pros,
+                resample=None if rates[b] is None else PolyStream(
+                    n_in, native, rates[b])))
+        return states
+
+    def _poly_reserve(self, rates) -> None:
+        """Device state of the streams' output rates for every tail slot
+        (cuda only; on the CPU each PolyStream keeps its own carry).
+        Called under _infer_lock, like _prosody_reserve."""
+        if self.device.type != "cuda":
+            return
+        from ..ops import PolyStreamState
+
+        for rate in set(rates) - {None}:
+            if rate not in self._poly_states:
+                self._poly_states[rate] = PolyStreamState(
+                    self.config.sample_rate, rate, self.device)
+        for st in self._poly_states.values():
+            st.reserve(self._tails.shape[0])
 
     def _prosody_reserve(self) -> None:
         """Device state of stream prosody for every tail slot (cuda only;
@@ -674,6 +706,7 @@ class VitsVoice(SonataModel):
                     self._tail_free.append(s.slot)
                     s.slot = None
                 s.prosody = None
+                s.resample = None
                 s.done = True
 
     def _tail_slots_take(self, n: int) -> List[int]:
@@ -704,7 +737,7 @@ class VitsVoice(SonataModel):
         holds _infer_lock.  Returns what _round_collect needs, or None when
         no state is live."""
         from ..ops import (gather_windows, pcm16_rows, prosody_stream_rows,
-                           stream_seam_rows)
+                           resample_poly_stream_rows, stream_seam_rows)
 
         live = [s for s in states if not s.done]
         if not live:
@@ -749,6 +782,18 @@ class VitsVoice(SonataModel):
                 out, out_len = prosody_stream_rows(
                     out, out_len, [s.prosody for s in live],
                     [s.slot for s in live], self._prosody_state,
+                    last=[sp.is_last for sp in specs])
+            # one launch per output rate; the other rows ride as copies
+            for rate in sorted({s.resample.rate_out for s in live
+                                if s.resample is not None}):
+                st = self._poly_states.get(rate)
+                if st is not None:
+                    st.reserve(self._tails.shape[0])
+                out, out_len = resample_poly_stream_rows(
+                    out, out_len,
+                    [s.resample if s.resample is not None
+                     and s.resample.rate_out == rate else None for s in live],
+                    [s.slot for s in live], st,
                     last=[sp.is_last for sp in specs])
             if pcm:
                 out, _ = pcm16_rows(out, out_len)
@@ -816,7 +861,8 @@ class VitsVoice(SonataModel):
 
     def stream_synthesis_batch(self, phonemes_batch: Sequence[str],
                                chunk_size=45, chunk_padding: int = 3,
-                               pcm: bool = False, prosody=None):
+                               pcm: bool = False, prosody=None,
+                               sample_rate=None):
         """stream_synthesis for a list of sentences at once: yields (index,
         chunk) with, per index, the chunk boundaries, total length and seams
         of stream_synthesis.  One encoder call, then one decode per round
@@ -826,9 +872,12 @@ class VitsVoice(SonataModel):
         yield; closing the iterator releases the streams' slots.
         `prosody` is stream_open's: with a triple, an index's chunks
         concatenate to the one-shot prosody of its plain stream, and a chunk
-        may be empty (every live stream still yields one per round)."""
+        may be empty (every live stream still yields one per round).
+        `sample_rate` is stream_open's too: an index's chunks then
+        concatenate to ops.resample_rows of its stream without a rate, and
+        a chunk may be empty."""
         states = self.stream_open(phonemes_batch, chunk_size, chunk_padding,
-                                  prosody=prosody)
+                                  prosody=prosody, sample_rate=sample_rate)
         pins = _PinnedPair() if self.device.type == "cuda" else None
         try:
             with self._infer_lock:
@@ -858,9 +907,10 @@ class StreamState:
     its previous chunk left."""
 
     __slots__ = ("index", "z", "row", "frames", "g", "slot", "prev_ext",
-                 "done", "prosody", "_plan", "_next")
+                 "done", "prosody", "resample", "_plan", "_next")
 
-    def __init__(self, index, z, row, frames, g, plan, slot, prosody=None):
+    def __init__(self, index, z, row, frames, g, plan, slot, prosody=None,
+                 resample=None):
         self.index = index
         self.z = z
         self.row = row
@@ -868,6 +918,7 @@ class StreamState:
         self.g = g
         self.slot = slot
         self.prosody = prosody  # audio.prosody.StreamProsody or None
+        self.resample = resample  # audio.resample.PolyStream or None
         self.prev_ext = 0
         self.done = False
         self._plan = plan

@@ -82,4 +82,6 @@ from .functional import (  # noqa: F401,E402
     resample_stream_rows,
     wsola_stream_rows,
     prosody_stream_rows,
+    PolyStreamState,
+    resample_poly_stream_rows,
 )

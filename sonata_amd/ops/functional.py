@@ -1251,3 +1251,97 @@ def prosody_stream_rows(x: torch.Tensor, lengths, procs, slots,
                   and (pl.do_speed or not pl.do_pitch) else 1.0
                   for pl in plans])
     return y, cur
+
+
+# --------------------------------------------------------------------------- #
+# streaming output sample-rate conversion (csrc/resample.hip,
+# resample_poly_stream_rows): the polyphase FIR of audio.resample for realtime
+# streams, one launch per round for all live streams of one output rate, the
+# carry on the device indexed by the streams' tail slots.  Every length comes
+# from audio.resample.PolyStreamPlan; PolyStream.push row by row is the CPU
+# path.  The kernel's tap loop is resample_rows' own, so a stream's chunks
+# concatenate to resample_rows of its whole input bit for bit.
+# --------------------------------------------------------------------------- #
+class PolyStreamState:
+    """Device state of streaming sample-rate conversion for one rate pair,
+    indexed by slot: `carry` f32 [S, 2, Kc], Kc = round_up(K - 1, 4).  The
+    two buffers of a slot are used in turn (a push reads one and writes the
+    other, see the kernel).  A stream's first push names no carry, so a slot
+    needs no cleaning between streams."""
+
+    def __init__(self, rate_in: int, rate_out: int, device):
+        from ..audio import resample as R
+
+        self.d = R.design(rate_in, rate_out)
+        self.rate_in, self.rate_out = self.d.rate_in, self.d.rate_out
+        self.device = torch.device(device)
+        self.carry_cap = _round_up(self.d.K - 1, 4)
+        self.slots = 0
+        self.carry = None
+
+    def reserve(self, slots: int) -> None:
+        """Grow to at least `slots` slots, keeping what live streams hold."""
+        if slots <= self.slots:
+            return
+        new = torch.zeros((slots, 2, self.carry_cap), dtype=torch.float32,
+                          device=self.device)
+        if self.carry is not None:
+            new[: self.carry.shape[0]].copy_(self.carry)
+        self.carry = new
+        self.slots = slots
+
+
+def resample_poly_stream_rows(x: torch.Tensor, lengths, streams, slots,
+                              state: Optional[PolyStreamState], last=None):
+    """One round of streaming sample-rate conversion for R streams: x [R, N]
+    f32 holds each stream's next chunk (lengths[r] samples), streams[r] its
+    audio.resample.PolyStream (None: the row is copied), slots[r] its slot
+    in `state`, last[r] whether this is the stream's final chunk.  All
+    streams named share state's rate pair.  Returns (y [R, n_out]
+    zero-padded, n_out a multiple of 8 and at least 8, out_lengths); a row
+    may emit nothing this round.  Over its rounds a row's outputs are those
+    of resample_rows on its whole input.  On the CPU each row goes through
+    PolyStream.push."""
+    R = x.shape[0]
+    lens = _row_lengths(lengths, R)
+    assert all(0 <= n <= x.shape[1] for n in lens), "length outside the row"
+    last = [False] * R if last is None else [bool(v) for v in last]
+    assert len(streams) == R and len(last) == R
+    if not use_hip(x):
+        import numpy as np
+
+        xn = x.detach().cpu().numpy()
+        rows = [xn[r, : lens[r]].copy() if streams[r] is None
+                else streams[r].push(xn[r, : lens[r]], last[r])
+                for r in range(R)]
+        out = [int(r.shape[0]) for r in rows]
+        y = np.zeros((R, max(_round_up(max(out, default=0), 8), 8)),
+                     dtype=np.float32)
+        for r, row in enumerate(rows):
+            y[r, : out[r]] = row
+        return (torch.from_numpy(y).to(x.device),
+                torch.tensor(out, dtype=torch.long))
+    if not any(s is not None for s in streams):
+        return x, torch.tensor(lens, dtype=torch.long)
+    assert state is not None, "device streams need a PolyStreamState"
+    slots = _per_row_int(slots, R)
+    d = state.d
+    for s in streams:
+        assert s is None or (s.rate_in, s.rate_out) == (
+            state.rate_in, state.rate_out), "stream of another rate pair"
+    assert max(slots) < state.slots, "slot outside the reserved state"
+    par, out = [], []
+    for n, s, slot, l in zip(lens, streams, slots, last):
+        if s is None:
+            par += [slot, n, 0, 0, 0, n, 0, n, 1, n, 0, 0]
+            out.append(n)
+            continue
+        p = s.plan.push(n, l)
+        par += [slot, p.m, p.a0, p.carry_pos, p.carry_len, p.n, p.e0, p.e1,
+                0, p.keep_pos, p.keep_len, p.parity]
+        out.append(p.e1 - p.e0)
+    n_out = max(_round_up(max(out, default=0), 8), 8)
+    y = hip_ext(required=True).resample_poly_stream_rows(
+        x.contiguous(), par, state.carry, _resample_bank(d, x.device),
+        d.L, d.M, d.H, n_out)
+    return y, torch.tensor(out, dtype=torch.long)

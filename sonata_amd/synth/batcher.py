@@ -163,12 +163,13 @@ class _StreamHandle:
     once opened, its model state."""
 
     __slots__ = ("phonemes", "chunk_size", "chunk_padding", "pcm", "q",
-                 "cancelled", "state", "prosody")
+                 "cancelled", "state", "prosody", "sample_rate")
 
     def __init__(self, phonemes, chunk_size, chunk_padding, pcm,
-                 prosody=None):
+                 prosody=None, sample_rate=None):
         self.phonemes = phonemes
         self.prosody = tuple(prosody) if prosody is not None else None
+        self.sample_rate = sample_rate
         self.chunk_size = int(chunk_size)
         self.chunk_padding = int(chunk_padding)
         self.pcm = bool(pcm)
@@ -240,7 +241,8 @@ class StreamBatcher:
         self._worker.start()
 
     def open(self, phonemes: str, chunk_size: int = 45,
-             chunk_padding: int = 3, pcm: bool = False, prosody=None):
+             chunk_padding: int = 3, pcm: bool = False, prosody=None,
+             sample_rate: Optional[int] = None):
         """Start one stream; returns the iterator of its chunks (float32
         arrays, or int16 with pcm=True), those model.stream_synthesis
         yields for the same arguments.
@@ -248,10 +250,24 @@ class StreamBatcher:
         over the stream by the model (stream_open(prosody=...)); streams of
         one round may each carry their own.  The chunks then concatenate to
         the one-shot prosody of the plain stream; rounds in which the
-        stretcher emits nothing yield no chunk."""
+        stretcher emits nothing yield no chunk.
+        `sample_rate`: optional output rate of this stream, converted by
+        the model inside the shared round (stream_open(sample_rate=...));
+        streams of one round may each carry their own.  The chunks then
+        concatenate to the conversion of the whole stream, and rounds in
+        which the filter emits nothing yield no chunk.  A rate the filter
+        does not serve raises ValueError here."""
         if self._closed:
             raise RuntimeError("stream batcher closed")
-        h = _StreamHandle(phonemes, chunk_size, chunk_padding, pcm, prosody)
+        if sample_rate is not None:
+            native = self.model.audio_output_info().sample_rate
+            if is_identity(native, sample_rate):
+                sample_rate = None
+            else:
+                check_rate(native, sample_rate)
+                sample_rate = int(sample_rate)
+        h = _StreamHandle(phonemes, chunk_size, chunk_padding, pcm, prosody,
+                          sample_rate)
         self._q.put(h)
         return _StreamIter(h)
 
@@ -305,6 +321,8 @@ class StreamBatcher:
             try:
                 kw = {"prosody": [h.prosody for h in group]} if any(
                     h.prosody is not None for h in group) else {}
+                if any(h.sample_rate is not None for h in group):
+                    kw["sample_rate"] = [h.sample_rate for h in group]
                 states = self.model.stream_open(
                     [h.phonemes for h in group],
                     [h.chunk_size for h in group], pad, **kw)
@@ -346,7 +364,8 @@ class StreamBatcher:
         by_state = {id(h.state): h for h in bucket}
         for state, chunk in chunks:
             h = by_state[id(state)]
-            if len(chunk) or h.prosody is None:
+            if len(chunk) or (h.prosody is None
+                              and h.sample_rate is None):
                 h.q.put(chunk)
         still = []
         for h in bucket:

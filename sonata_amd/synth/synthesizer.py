@@ -134,6 +134,17 @@ class SonataSpeechSynthesizer:
             raise ValueError(
                 "SONATA_STREAM_PROSODY must be 'chunk' or 'continuous', "
                 f"not {self.stream_prosody!r}")
+        # output sample rate of synthesize_streamed: "host" converts every
+        # chunk here with one audio.resample.StreamResampler per sentence;
+        # "device" hands the rate to the model's batched stream path, which
+        # converts inside the shared round (other chunk boundaries, and the
+        # last bits of f32 accumulation instead of f64)
+        self.stream_resample = os.environ.get("SONATA_STREAM_RESAMPLE",
+                                              "host") or "host"
+        if self.stream_resample not in ("host", "device"):
+            raise ValueError(
+                "SONATA_STREAM_RESAMPLE must be 'host' or 'device', "
+                f"not {self.stream_resample!r}")
 
     # ------------------------------------------------------------------ #
     def audio_output_info(self) -> AudioInfo:
@@ -336,7 +347,12 @@ class SonataSpeechSynthesizer:
         An output sample rate is served by one audio.resample
         StreamResampler per sentence, on the host, after prosody in either
         mode: it is flushed at the end of the sentence, its empty chunks are
-        dropped and silence is counted at the output rate."""
+        dropped and silence is counted at the output rate.
+        With stream_resample == "device" (and a model with batched streams)
+        the rate rides into the model's stream path instead, after prosody
+        there: no StreamResampler is built and empty chunks are dropped.
+        It applies when no prosody is left to run here, on the host, which
+        would have to come before the conversion."""
         rate = self.output_rate(output_config)
         phonemes = self.model.phonemize_text(text)
         info = self.model.audio_output_info()
@@ -350,6 +366,14 @@ class SonataSpeechSynthesizer:
                 and self.model.supports_streaming_output
                 and hasattr(self.model, "stream_synthesis_batch")):
             triple = output_config.prosody_triple()
+        if self.stream_resample not in ("host", "device"):
+            raise ValueError(f"stream_resample {self.stream_resample!r}")
+        host_prosody = (triple is None and output_config is not None
+                        and not output_config.is_noop)
+        model_rate = (rate is not None and self.stream_resample == "device"
+                      and not host_prosody
+                      and self.model.supports_streaming_output
+                      and hasattr(self.model, "stream_synthesis_batch"))
 
         def producer():
             try:
@@ -364,15 +388,18 @@ class SonataSpeechSynthesizer:
                     # (faster) chunks; the in-sentence chunker grows
                     # further.  The 1024 cap matches MAX_CHUNK_SIZE.
                     cs = min(chunk_size * (n_done + 1), 1024)
-                    if triple is not None:
+                    if triple is not None or model_rate:
+                        kw = {"sample_rate": rate} if model_rate else {}
                         if self.stream_batcher is not None:
                             it = self.stream_batcher.open(
-                                sent, cs, chunk_padding, prosody=triple)
+                                sent, cs, chunk_padding, prosody=triple,
+                                **kw)
                         else:
                             it = (c for _, c in
                                   self.model.stream_synthesis_batch(
                                       [sent], cs, chunk_padding,
-                                      prosody=[triple]))
+                                      prosody=(None if triple is None
+                                               else [triple]), **kw))
                     elif (self.stream_batcher is not None
                             and self.model.supports_streaming_output):
                         it = self.stream_batcher.open(sent, cs, chunk_padding)
@@ -383,15 +410,15 @@ class SonataSpeechSynthesizer:
                     else:
                         it = iter([self.model.speak_one_sentence(sent).samples])
                     rs = (StreamResampler(info.sample_rate, rate)
-                          if rate is not None else None)
+                          if rate is not None and not model_rate else None)
                     for chunk in it:
                         if triple is None and output_config is not None \
                                 and not output_config.is_noop:
                             chunk = output_config.apply(chunk, info.sample_rate)
                         if rs is not None:
                             chunk = rs.push(chunk)
-                        if (triple is not None or rs is not None) \
-                                and not len(chunk):
+                        if (triple is not None or rs is not None
+                                or model_rate) and not len(chunk):
                             continue
                         q.put(chunk)
                     if rs is not None:
