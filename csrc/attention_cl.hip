@@ -18,6 +18,9 @@
 //   qkv  [B][T][3][H*D]   packed rows from ONE fused linear
 //   rel_k/rel_v [2w+1][D] (heads share the table, vits.py:84-90)
 //   out  [B][T][H*D]
+// lens masks KEYS only: query rows t >= lens[b] are still computed (finite,
+// unlike the eager chain's; the encoder multiplies them by zero) and valid
+// rows never depend on what the padded qkv rows hold.
 // Oracle: sonata_amd/models/vits.py RelativeAttention.forward_cl
 // (reference semantics: upstream VITS attentions.py via the ONNX graph,
 //  SURVEY.md section 2.2 TextEncoder row).
@@ -307,22 +310,45 @@ torch::Tensor attn_relpos_cl(torch::Tensor qkv, torch::Tensor rel_k,
   TORCH_CHECK(qkv.dim() == 3 && qkv.is_cuda() && qkv.is_contiguous(),
               "attn: qkv must be [B,T,3*H*D] contiguous cuda");
   TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, "attn: bf16 only");
-  const long B = qkv.size(0), T = qkv.size(1);
-  TORCH_CHECK(qkv.size(2) % (3 * H) == 0);
-  const long D = qkv.size(2) / (3 * H);
-  TORCH_CHECK(D % 8 == 0 && D <= 128, "attn: head_dim must be <=128, 8|D");
-  TORCH_CHECK(rel_k.is_contiguous() && rel_v.is_contiguous());
-  TORCH_CHECK(rel_k.size(-1) == D && rel_v.size(-1) == D);
+  TORCH_CHECK(H >= 1, "attn: heads must be >= 1");
+  TORCH_CHECK(window >= 0, "attn: window must be >= 0");
   TORCH_CHECK(2 * window + 1 <= ATT_SLOTS, "attn: window too large");
+  const long B = qkv.size(0), T = qkv.size(1);
+  TORCH_CHECK(qkv.size(2) % (3 * H) == 0,
+              "attn: qkv channels must be a multiple of 3*heads");
+  const long D = qkv.size(2) / (3 * H);
+  TORCH_CHECK(D % 8 == 0 && D <= 128,
+              "attn: head_dim must be <=128, 8|D");
+  // the kernel reads rel_k/rel_v[s*D + d] for every s < 2w+1 on the device
+  TORCH_CHECK(rel_k.dim() == 2 && rel_v.dim() == 2 &&
+                  rel_k.size(0) == 2 * window + 1 &&
+                  rel_v.size(0) == 2 * window + 1,
+              "attn: rel tables must be [2*window+1, D]");
+  TORCH_CHECK(rel_k.size(1) == D && rel_v.size(1) == D,
+              "attn: rel tables must be [2*window+1, D]");
+  TORCH_CHECK(rel_k.is_contiguous() && rel_v.is_contiguous(),
+              "attn: rel tables must be contiguous");
   TORCH_CHECK(rel_k.scalar_type() == at::kBFloat16 &&
-              rel_v.scalar_type() == at::kBFloat16);
-  auto out = torch::empty({B, T, H * D}, qkv.options());
-  if (out.numel() == 0) return out;
+                  rel_v.scalar_type() == at::kBFloat16,
+              "attn: rel tables must be bf16");
+  TORCH_CHECK(rel_k.is_cuda() && rel_v.is_cuda() &&
+                  rel_k.device() == qkv.device() &&
+                  rel_v.device() == qkv.device(),
+              "attn: rel tables must be on qkv's device");
   const int* lens_p = nullptr;
   if (lens.has_value()) {
-    TORCH_CHECK(lens->scalar_type() == at::kInt && lens->is_cuda());
+    // the kernel reads lens[b] for every b < B on the device
+    TORCH_CHECK(lens->scalar_type() == at::kInt,
+                "attn: lens must be int32");
+    TORCH_CHECK(lens->is_cuda() && lens->device() == qkv.device(),
+                "attn: lens must be on qkv's device");
+    TORCH_CHECK(lens->dim() == 1 && lens->size(0) == B &&
+                    lens->is_contiguous(),
+                "attn: lens must be [B] contiguous");
     lens_p = lens->data_ptr<int>();
   }
+  auto out = torch::empty({B, T, H * D}, qkv.options());
+  if (out.numel() == 0) return out;
   hipStream_t st = attn_stream();
   dim3 grid(ceil_div(T, ATT_BM), H, B);
 #define LAUNCH_ATT(DPAD)                                                     \
