@@ -123,6 +123,9 @@ torch::Tensor resample_stream_rows(torch::Tensor x, std::vector<int64_t> par,
 std::vector<torch::Tensor> pcm16_rows(torch::Tensor x, torch::Tensor len,
                                       long N_out, bool peak_normalize);
 long pcm_tile();
+std::vector<torch::Tensor> g711_rows(torch::Tensor x, torch::Tensor len,
+                                     torch::Tensor law, long N_out,
+                                     bool peak_normalize);
 // resample.hip
 torch::Tensor resample_poly_rows(torch::Tensor x, torch::Tensor in_len,
                                  torch::Tensor out_len, torch::Tensor bank,
@@ -248,6 +251,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("len"), py::arg("n_out"),
         py::arg("peak_normalize") = true);
   m.attr("PCM_TILE") = pcm_tile();
+  m.def("g711_rows", &g711_rows,
+        "per-row peak-normalised G.711 codes of [B,N] f32/bf16; law is "
+        "int32 [B], 0 = mu-law, 1 = A-law; returns (codes uint8 [B,n_out], "
+        "peaks)",
+        py::arg("x"), py::arg("len"), py::arg("law"), py::arg("n_out"),
+        py::arg("peak_normalize") = true);
   m.def("resample_poly_rows", &resample_poly_rows,
         "per-row polyphase FIR sample-rate conversion of [B,N] f32/bf16 by "
         "L/M; bank is the [K][L] f32 filter; returns y [B,n_out] f32",

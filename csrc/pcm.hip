@@ -12,6 +12,10 @@
 // Columns at or past len[b] are written as 0, so appended silence is free:
 // the host slices len + silence samples out of a row.
 //
+// g711_rows writes 8-bit G.711 instead: the mu-law or A-law code of that
+// int16 (sonata_amd/audio/g711.py encode, bit for bit), companded in the
+// same pass, with the row's code of sample 0 in place of the zeros.
+//
 // Rows start at x + b*stride and y + b*N_out: nothing is assumed about
 // their alignment.  Each tile is split by ADDRESS into a scalar head up to
 // the next 16-byte boundary, a 16-byte vector body and a scalar tail.
@@ -172,6 +176,112 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm16_rows_kernel(
   }
 }
 
+// --------------------------------------------------------------------------
+// g711_rows: grid (output tiles, B).  to_pcm_ of the row, then G.711
+// companding in integer VALU: the device counterpart of
+// sonata_amd/audio/g711.py encode (the Sun/CCITT g711.c forms), bit for bit.
+// The law is per row (0 = mu-law, anything else = A-law; the caller checks
+// the values on the host), so the branch is uniform over the workgroup.
+// The split is made on the OUTPUT address: 16 codes per 16-byte store, at
+// most one vector group per lane of a tile.  Columns at or past len[b] are
+// written as the row's code of sample 0 (0xFF / 0xD5), not 0.
+// --------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+
+// bit length of v > 0
+__device__ __forceinline__ int bitlen_(int v) { return 32 - __clz(v); }
+
+__device__ __forceinline__ unsigned ulaw_(int x) {
+  const int s = x >> 2;                           // 14-bit magnitude domain
+  const int m = min(abs(s) + 33, 0x1FFF);         // bias, clip: 33 .. 8191
+  const int seg = bitlen_(m) - 6;                 // 0 .. 7
+  return (unsigned)((seg << 4) | ((m >> (seg + 1)) & 0xF)) ^
+         (s < 0 ? 0x7Fu : 0xFFu);
+}
+
+__device__ __forceinline__ unsigned alaw_(int x) {
+  const int ix = (x < 0 ? ~x : x) >> 4;           // 0 .. 2047
+  const int e = bitlen_(ix | 16) - 4;             // 1 .. 7 for ix >= 16
+  int c = ix < 16 ? ix : ((ix >> (e - 1)) - 16) + (e << 4);
+  if (x >= 0) c |= 0x80;
+  return (unsigned)c ^ 0x55u;
+}
+
+__device__ __forceinline__ unsigned g711_(int x, bool alaw) {
+  return alaw ? alaw_(x) : ulaw_(x);
+}
+
+template <typename T>
+__global__ __launch_bounds__(PCM_THREADS) void g711_rows_kernel(
+    const T* __restrict__ x, long stride, const int* __restrict__ len,
+    const int* __restrict__ law, const unsigned* __restrict__ peaks,
+    unsigned char* __restrict__ y, long N, long N_out) {
+  constexpr int V = PcmVec<T>::V;
+  __shared__ float scale_s;
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x;
+  const long n = min(min(max((long)len[b], 0L), N), N_out);
+  const long o0 = (long)blockIdx.x * PCM_TILE;
+  if (o0 >= N_out) return;  // uniform over the workgroup
+  const int cnt = (int)(min(N_out, o0 + PCM_TILE) - o0);
+  const T* xr = x + (long)b * stride;  // read at indices < n only
+  unsigned char* yr = y + (long)b * N_out;
+  const bool alaw = law[b] != 0;                  // row-uniform
+  const unsigned zero = alaw ? 0xD5u : 0xFFu;     // code of sample 0
+
+  if (tid == 0) {
+    float s = 32767.f;
+    if (peaks != nullptr) {
+      const double pk = (double)__uint_as_float(peaks[b]);
+      s = pk > 1e-8 ? (float)(32767.0 / pk) : 0.f;
+    }
+    scale_s = s;
+  }
+  __syncthreads();
+  const float scale = scale_s;
+
+  const int head = min(cnt, head_elems_(yr + o0));
+  const int nvec = (cnt - head) / 16;  // <= PCM_THREADS: one group per lane
+  const int tail0 = head + nvec * 16;
+  if (tid < head) {
+    const long i = o0 + tid;
+    yr[i] = (unsigned char)(
+        i < n ? g711_(to_pcm_(ld_f<T>(xr + i), scale), alaw) : zero);
+  }
+  const long body = o0 + head;
+  const bool x_aligned =
+      (reinterpret_cast<uintptr_t>(xr + body) & 15) == 0;  // row-uniform
+  if (tid < nvec) {
+    const long i = body + (long)tid * 16;
+    unsigned c[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) c[j] = zero;
+    if (i + 16 <= n && x_aligned) {
+      float e[16];
+#pragma unroll
+      for (int q = 0; q < 16 / V; ++q)
+        PcmVec<T>::load(xr + i + q * V, e + q * V);
+#pragma unroll
+      for (int j = 0; j < 16; ++j) c[j] = g711_(to_pcm_(e[j], scale), alaw);
+    } else if (i < n) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (i + j < n) c[j] = g711_(to_pcm_(ld_f<T>(xr + i + j), scale), alaw);
+    }
+    u32x4 out;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)  // byte j of the store is code j
+      out[w] = c[4 * w] | (c[4 * w + 1] << 8) | (c[4 * w + 2] << 16) |
+               (c[4 * w + 3] << 24);
+    *reinterpret_cast<u32x4*>(yr + i) = out;
+  }
+  if (tail0 + tid < cnt) {
+    const long i = o0 + tail0 + tid;
+    yr[i] = (unsigned char)(
+        i < n ? g711_(to_pcm_(ld_f<T>(xr + i), scale), alaw) : zero);
+  }
+}
+
 // ------------------------------ host wrapper --------------------------------
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -217,6 +327,54 @@ std::vector<torch::Tensor> pcm16_rows(torch::Tensor x, torch::Tensor len,
                          len.data_ptr<int>(),
                          peak_normalize ? (const unsigned*)pk : nullptr,
                          y.data_ptr<short>(), N, N_out);
+  });
+  return {y, peaks};
+}
+
+// g711_rows: x and len as pcm16_rows takes them, law int32 [B] (0 = mu-law,
+// 1 = A-law; values are checked on the host before upload, the kernel reads
+// any other value as A-law).  Returns (y uint8 [B, N_out], peaks f32 [B]).
+std::vector<torch::Tensor> g711_rows(torch::Tensor x, torch::Tensor len,
+                                     torch::Tensor law, long N_out,
+                                     bool peak_normalize) {
+  TORCH_CHECK(x.dim() == 2 && x.is_cuda() &&
+                  (x.scalar_type() == at::kFloat ||
+                   x.scalar_type() == at::kBFloat16),
+              "g711_rows: x must be a cuda f32 or bf16 [B, N] tensor");
+  const long B = x.size(0), N = x.size(1);
+  TORCH_CHECK(N <= 1 || x.stride(1) == 1,
+              "g711_rows: rows must be contiguous");
+  TORCH_CHECK(x.stride(0) >= 0, "g711_rows: negative row stride");
+  TORCH_CHECK(len.is_cuda() && len.is_contiguous() &&
+                  len.scalar_type() == at::kInt && len.dim() == 1 &&
+                  len.size(0) == B && len.device() == x.device(),
+              "g711_rows: len must be a cuda int32 [B] tensor");
+  TORCH_CHECK(law.is_cuda() && law.is_contiguous() &&
+                  law.scalar_type() == at::kInt && law.dim() == 1 &&
+                  law.size(0) == B && law.device() == x.device(),
+              "g711_rows: law must be a cuda int32 [B] tensor");
+  TORCH_CHECK(N < INT_MAX && N_out >= 0 && N_out < INT_MAX && B < 65536,
+              "g711_rows: shape out of range");
+  auto y = torch::empty({B, N_out}, x.options().dtype(at::kByte));
+  auto peaks = torch::empty({B}, x.options().dtype(at::kFloat));
+  if (B == 0) return {y, peaks};
+  hipStream_t stream = at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+  unsigned* pk = reinterpret_cast<unsigned*>(peaks.data_ptr<float>());
+  HIP_CHECK(hipMemsetAsync(pk, 0, B * sizeof(unsigned), stream));
+  const long stride = x.stride(0);
+  DISPATCH_FT_CONV(x, {
+    const scalar_t* xp = reinterpret_cast<const scalar_t*>(x.data_ptr());
+    if (peak_normalize && N > 0)
+      hipLaunchKernelGGL(absmax_rows_kernel<scalar_t>,
+                         dim3(ceil_div(N, PCM_TILE), B), dim3(PCM_THREADS), 0,
+                         stream, xp, stride, len.data_ptr<int>(), pk, N);
+    if (N_out > 0)
+      hipLaunchKernelGGL(g711_rows_kernel<scalar_t>,
+                         dim3(ceil_div(N_out, PCM_TILE), B),
+                         dim3(PCM_THREADS), 0, stream, xp, stride,
+                         len.data_ptr<int>(), law.data_ptr<int>(),
+                         peak_normalize ? (const unsigned*)pk : nullptr,
+                         y.data_ptr<uint8_t>(), N, N_out);
   });
   return {y, peaks};
 }

@@ -64,8 +64,41 @@ def write_wav_file_pcm(path: str, pcm, sample_rate: int,
         f.write(wav_bytes_pcm(pcm, sample_rate, num_channels))
 
 
+def wav_header_g711(data_bytes: int, sample_rate: int, law: str,
+                    num_channels: int = 1) -> bytes:
+    """58-byte RIFF/WAVE header for a G.711 payload of `data_bytes`: the
+    non-PCM layout, an 18-byte fmt chunk (tag 7 mu-law / 6 A-law, 8 bits,
+    cbSize 0) and a fact chunk with the sample count per channel.  The RIFF
+    size counts the pad byte an odd payload gets."""
+    from .g711 import WAVE_TAG, check_law
+
+    tag = WAVE_TAG[check_law(law)]
+    return (b"RIFF" + struct.pack("<I", 50 + data_bytes + (data_bytes & 1))
+            + b"WAVE"
+            + b"fmt " + struct.pack("<IHHIIHHH", 18, tag, num_channels,
+                                    sample_rate, sample_rate * num_channels,
+                                    num_channels, 8, 0)
+            + b"fact" + struct.pack("<II", 4, data_bytes // num_channels)
+            + b"data" + struct.pack("<I", data_bytes))
+
+
+def wav_bytes_g711(codes, sample_rate: int, law: str,
+                   num_channels: int = 1) -> bytes:
+    """WAV file bytes for uint8 G.711 codes (audio.g711.encode)."""
+    codes = np.asarray(codes, dtype=np.uint8).reshape(-1).tobytes()
+    return (wav_header_g711(len(codes), sample_rate, law, num_channels)
+            + codes + b"\x00" * (len(codes) & 1))
+
+
+def write_wav_file_g711(path: str, codes, sample_rate: int, law: str,
+                        num_channels: int = 1) -> None:
+    with open(path, "wb") as f:
+        f.write(wav_bytes_g711(codes, sample_rate, law, num_channels))
+
+
 def read_wav_file(path: str):
-    """Read a 16-bit PCM WAV back to float32 in [-1,1]. Test helper."""
+    """Read a 16-bit PCM or 8-bit G.711 (tags 7 and 6, decoded) WAV back to
+    float32 in [-1,1]. Test helper."""
     with open(path, "rb") as f:
         data = f.read()
     assert data[:4] == b"RIFF" and data[8:12] == b"WAVE"
@@ -83,7 +116,14 @@ def read_wav_file(path: str):
             pcm = body
         pos += 8 + size + (size & 1)
     assert fmt is not None and pcm is not None
-    _, channels, rate, _, _, bits = fmt
+    tag, channels, rate, _, _, bits = fmt
+    if tag in (6, 7):
+        from .g711 import decode
+
+        assert bits == 8
+        x = decode(np.frombuffer(pcm, dtype=np.uint8),
+                   "ulaw" if tag == 7 else "alaw")
+        return x.astype(np.float32) / 32767.0, rate, channels
     assert bits == 16
     x = np.frombuffer(pcm, dtype="<i2").astype(np.float32) / 32767.0
     return x, rate, channels

@@ -10,6 +10,7 @@ trait-object hierarchy.
 from __future__ import annotations
 
 import abc
+import dataclasses
 from dataclasses import dataclass, field
 from typing import Dict, Iterator, List, Optional, Sequence
 
@@ -111,27 +112,53 @@ class PcmAudio:
     """A synthesized waveform already converted to wire format: `pcm` is
     the peak-normalised int16 that `Audio.as_wave_bytes` would produce for
     the float samples it came from (converted on the device by
-    speak_batch_pcm when available).  Offers front ends what Audio does."""
+    speak_batch_pcm when available).  Offers front ends what Audio does.
+
+    With `encoding` "ulaw" or "alaw", `pcm` is the uint8 G.711 codes of
+    that int16 (audio.g711.encode) and `info.sample_width` is 1."""
 
     pcm: np.ndarray
     info: AudioInfo
     inference_ms: float = 0.0
+    encoding: str = "pcm16"
 
     def __post_init__(self):
-        self.pcm = np.asarray(self.pcm, dtype=np.int16).reshape(-1)
+        if self.encoding == "pcm16":
+            self.pcm = np.asarray(self.pcm, dtype=np.int16).reshape(-1)
+            return
+        from .audio.g711 import check_law
+
+        check_law(self.encoding)
+        self.pcm = np.asarray(self.pcm, dtype=np.uint8).reshape(-1)
+        if self.info.sample_width != 1:
+            self.info = dataclasses.replace(self.info, sample_width=1)
 
     @classmethod
-    def from_audio(cls, audio: Audio, silence_samples: int = 0) -> "PcmAudio":
+    def from_audio(cls, audio: Audio, silence_samples: int = 0,
+                   encoding: str = "pcm16") -> "PcmAudio":
         """Host conversion: to_i16 of audio.samples followed by
         `silence_samples` zeros (equal to to_i16 of the samples with that
-        silence merged: zeros neither move the peak nor scale)."""
+        silence merged: zeros neither move the peak nor scale), then
+        g711.encode of it for a G.711 `encoding`."""
         from .audio.samples import to_i16
 
         pcm = to_i16(audio.samples)
         if silence_samples > 0:
             pcm = np.concatenate(
                 [pcm, np.zeros(silence_samples, dtype=np.int16)])
-        return cls(pcm, audio.info, audio.inference_ms)
+        if encoding != "pcm16":
+            from .audio.g711 import encode
+
+            pcm = encode(pcm, encoding)
+        return cls(pcm, audio.info, audio.inference_ms, encoding)
+
+    def to_int16(self) -> np.ndarray:
+        """The samples as int16: `pcm` itself, or the decoded codes."""
+        if self.encoding == "pcm16":
+            return self.pcm
+        from .audio.g711 import decode
+
+        return decode(self.pcm, self.encoding)
 
     @property
     def duration_ms(self) -> float:
@@ -143,9 +170,17 @@ class PcmAudio:
         return (self.inference_ms / d) if d > 0 else 0.0
 
     def as_wave_bytes(self) -> bytes:
+        if self.encoding != "pcm16":
+            return self.pcm.tobytes()
         return self.pcm.astype("<i2", copy=False).tobytes()
 
     def save_to_file(self, path: str) -> None:
+        if self.encoding != "pcm16":
+            from .audio.wav import write_wav_file_g711
+
+            write_wav_file_g711(path, self.pcm, self.info.sample_rate,
+                                self.encoding)
+            return
         from .audio.wav import write_wav_file_pcm
 
         write_wav_file_pcm(path, self.pcm, self.info.sample_rate)

@@ -40,6 +40,7 @@ class SynthesisRequest:
     volume: Optional[float] = None
     appended_silence_ms: Optional[float] = None
     sample_rate: Optional[int] = None
+    encoding: Optional[str] = None
 
     @staticmethod
     def from_json(line: str) -> "SynthesisRequest":
@@ -55,6 +56,7 @@ class SynthesisRequest:
             volume=d.get("volume"),
             appended_silence_ms=d.get("appended_silence_ms"),
             sample_rate=d.get("sample_rate"),
+            encoding=d.get("encoding"),
         )
 
 
@@ -83,6 +85,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="appended silence ms after each sentence")
     p.add_argument("--sample-rate", type=int, default=None,
                    help="output sample rate in Hz (default: the voice's own)")
+    p.add_argument("--encoding", default=None,
+                   choices=["pcm16", "ulaw", "alaw"],
+                   help="output encoding: 16-bit PCM (default) or 8-bit "
+                        "G.711 mu-law / A-law")
     p.add_argument("--chunk-size", type=int, default=100,
                    help="realtime first-chunk mel frames (reference default)")
     p.add_argument("--chunk-padding", type=int, default=3)
@@ -109,12 +115,14 @@ def _make_output_config(args, req: SynthesisRequest):
                else args.silence)
     sample_rate = (req.sample_rate if req.sample_rate is not None
                    else getattr(args, "sample_rate", None))
+    encoding = (req.encoding if req.encoding is not None
+                else getattr(args, "encoding", None))
     if rate is None and pitch is None and volume is None and silence is None \
-            and sample_rate is None:
+            and sample_rate is None and encoding is None:
         return None
     return AudioOutputConfig(rate=rate, volume=volume, pitch=pitch,
                              appended_silence_ms=silence,
-                             sample_rate=sample_rate)
+                             sample_rate=sample_rate, encoding=encoding)
 
 
 def _apply_synth_config(voice, args, req: SynthesisRequest) -> None:
@@ -146,6 +154,8 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
     out_rate = (int(out_cfg.sample_rate)
                 if out_cfg is not None and out_cfg.sample_rate
                 else info.sample_rate)
+    # "pcm16", or the G.711 law the int16 written below is companded with
+    enc = synth.output_encoding(out_cfg)
     total = 0
     if args.output_file:
         path = _enumerate_path(args.output_file, n)
@@ -159,20 +169,32 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
             # stream chunks to stdout AS THEY ARRIVE (reference cli
             # main.rs:160-176): WAV header first (size patched only when
             # stdout is seekable), then i16 PCM per chunk
-            from ..audio.samples import to_i16_bytes
-            from ..audio.wav import wav_header
+            from ..audio import g711
+            from ..audio.samples import to_i16, to_i16_bytes
+            from ..audio.wav import wav_header, wav_header_g711
+
+            def header(n: int) -> bytes:
+                if enc != "pcm16":
+                    return wav_header_g711(n, out_rate, enc)
+                return wav_header(n * 2, out_rate)
 
             header_pos = stdout.tell() if stdout.seekable() else None
-            stdout.write(wav_header(0, out_rate))
+            stdout.write(header(0))
             for chunk in synth.synthesize_streamed(
                     req.text, out_cfg, args.chunk_size, args.chunk_padding):
-                stdout.write(to_i16_bytes(chunk, peak_normalize=False))
+                if enc != "pcm16":
+                    stdout.write(g711.encode(
+                        to_i16(chunk, peak_normalize=False), enc).tobytes())
+                else:
+                    stdout.write(to_i16_bytes(chunk, peak_normalize=False))
                 stdout.flush()
                 total += len(chunk)
             if header_pos is not None:
+                if enc != "pcm16" and total & 1:
+                    stdout.write(b"\x00")  # RIFF pad of an odd data chunk
                 end = stdout.tell()
                 stdout.seek(header_pos)
-                stdout.write(wav_header(total * 2, out_rate))
+                stdout.write(header(total))
                 stdout.seek(end)
             stdout.flush()
             return total
@@ -184,7 +206,15 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
             samples = (np.concatenate(parts) if parts
                        else np.zeros(0, dtype=np.float32))
         total = len(samples)
-        stdout.write(wav_bytes(samples, out_rate))
+        if enc != "pcm16":
+            from ..audio import g711
+            from ..audio.samples import to_i16
+            from ..audio.wav import wav_bytes_g711
+
+            stdout.write(wav_bytes_g711(g711.encode(to_i16(samples), enc),
+                                        out_rate, enc))
+        else:
+            stdout.write(wav_bytes(samples, out_rate))
         stdout.flush()
     return total
 

@@ -118,6 +118,8 @@ def _build_file() -> descriptor_pb2.FileDescriptorProto:
         (3, "pitch", "uint32", "optional"),
         (4, "appended_silence_ms", "uint32", "optional"),
         (5, "sample_rate", "uint32", "optional"),
+        # 0 = pcm16, 1 = ulaw, 2 = alaw (wire encoding of wav_samples)
+        (6, "encoding", "uint32", "optional"),
     ])
     message("Utterance", [
         (1, "voice_id", "string", None),

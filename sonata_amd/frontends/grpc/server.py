@@ -37,6 +37,8 @@ log = logging.getLogger("sonata.grpc")
 DEFAULT_PORT = 49314
 REALTIME_CHUNK_SIZE = 55   # reference main.rs:383
 REALTIME_CHUNK_PADDING = 3
+# SpeechArgs.encoding numbers
+WIRE_ENCODINGS = {0: "pcm16", 1: "ulaw", 2: "alaw"}
 
 __version__ = "0.1.0"
 
@@ -138,17 +140,22 @@ class SonataGrpcService:
                                  else None),
             sample_rate=(args.sample_rate if args.HasField("sample_rate")
                          else None),
+            # an unknown number stays a number: _output_rate refuses it
+            encoding=(WIRE_ENCODINGS.get(args.encoding, args.encoding)
+                      if args.HasField("encoding") else None),
         )
         if cfg.is_noop and cfg.appended_silence_ms is None \
-                and cfg.sample_rate is None:
+                and cfg.sample_rate is None and cfg.encoding is None:
             return None
         return cfg
 
     @staticmethod
     def _output_rate(v, out_cfg, context) -> Optional[int]:
         """The request's output rate when it differs from the voice's own;
-        a rate the filter does not serve ends the RPC."""
+        a rate the filter does not serve, or an unknown encoding, ends the
+        RPC."""
         try:
+            v.synth.output_encoding(out_cfg)
             return v.synth.output_rate(out_cfg)
         except ValueError as e:
             context.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
@@ -240,9 +247,11 @@ class SonataGrpcService:
         silence_ms = out_cfg.appended_silence_ms if out_cfg else None
         # the output rate rides along too; after host prosody it is
         # applied on the host as well
+        enc = v.synth.output_encoding(out_cfg)
         futures = [v.batcher.submit(sent, triple, pcm=pcm,
                                     silence_ms=silence_ms if pcm else None,
-                                    sample_rate=rate if pcm else None)
+                                    sample_rate=rate if pcm else None,
+                                    encoding=enc if pcm else None)
                    for sent in sentences]
         for f in futures:
             audio = f.result()
@@ -257,13 +266,19 @@ class SonataGrpcService:
         v = self._get(request.voice_id, context)
         out_cfg = self._speech_args_to_config(
             request.speech_args if request.HasField("speech_args") else None)
-        from ...audio.samples import to_i16_bytes
+        from ...audio import g711
+        from ...audio.samples import to_i16, to_i16_bytes
 
         self._output_rate(v, out_cfg, context)
+        enc = v.synth.output_encoding(out_cfg)
         for chunk in v.synth.synthesize_streamed(
                 request.text, out_cfg,
                 REALTIME_CHUNK_SIZE, REALTIME_CHUNK_PADDING):
-            yield MESSAGES["WaveSamples"](wav_samples=to_i16_bytes(chunk))
+            if enc != "pcm16":
+                wav = g711.encode(to_i16(chunk), enc).tobytes()
+            else:
+                wav = to_i16_bytes(chunk)
+            yield MESSAGES["WaveSamples"](wav_samples=wav)
 
 
 def _generic_handler(service: SonataGrpcService) -> grpc.GenericRpcHandler:

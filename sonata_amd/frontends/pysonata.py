@@ -36,17 +36,20 @@ class AudioOutputConfig:
                  volume: Optional[float] = None,
                  pitch: Optional[float] = None,
                  appended_silence_ms: Optional[float] = None,
-                 sample_rate: Optional[int] = None):
+                 sample_rate: Optional[int] = None,
+                 encoding: Optional[str] = None):
         self.rate = rate
         self.volume = volume
         self.pitch = pitch
         self.appended_silence_ms = appended_silence_ms
         self.sample_rate = sample_rate  # Hz; None: the voice's own rate
+        self.encoding = encoding  # None / "pcm16", or G.711 "ulaw" / "alaw"
 
     def _to_internal(self) -> _OutCfg:
         return _OutCfg(rate=self.rate, volume=self.volume, pitch=self.pitch,
                        appended_silence_ms=self.appended_silence_ms,
-                       sample_rate=self.sample_rate)
+                       sample_rate=self.sample_rate,
+                       encoding=self.encoding)
 
 
 class WaveSamples:
@@ -181,12 +184,17 @@ class Sonata:
                             audio_output_config: Optional[AudioOutputConfig]
                             = None, chunk_size: int = 45,
                             chunk_padding: int = 3) -> Iterator[bytes]:
-        from ..audio.samples import to_i16_bytes
+        from ..audio import g711
+        from ..audio.samples import to_i16, to_i16_bytes
 
         cfg = audio_output_config._to_internal() if audio_output_config else None
+        enc = self._synth.output_encoding(cfg)
         for chunk in self._synth.synthesize_streamed(text, cfg, chunk_size,
                                                      chunk_padding):
-            yield to_i16_bytes(chunk)
+            if enc != "pcm16":
+                yield g711.encode(to_i16(chunk), enc).tobytes()
+            else:
+                yield to_i16_bytes(chunk)
 
     def synthesize_to_file(self, filename: str, text: str,
                            audio_output_config: Optional[AudioOutputConfig]

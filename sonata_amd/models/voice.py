@@ -306,9 +306,53 @@ class VitsVoice(SonataModel):
         return (self.device.type == "cuda"
                 and os.environ.get("SONATA_DEVICE_PCM", "1") != "0")
 
+    @staticmethod
+    def _row_encodings(encoding, B: int):
+        """Per-row wire encoding: "pcm16", "ulaw" or "alaw"."""
+        from ..audio.g711 import check_encoding
+
+        if encoding is None or isinstance(encoding, str):
+            encoding = [encoding] * B
+        assert len(encoding) == B, "one encoding per row"
+        return [check_encoding(e) for e in encoding]
+
+    @staticmethod
+    def _wire_rows(y, lengths, sil, encs):
+        """Wire-format rows of y [b, n] on the device: ops.pcm16_rows for
+        the int16 rows and ONE ops.g711_rows (per-row laws) for the 8-bit
+        rows, each followed by its own host copy.  Returns one NumPy row per
+        input row, silence included."""
+        from ..ops import g711_rows, pcm16_rows
+
+        lens = [int(n) for n in (lengths.tolist()
+                                 if isinstance(lengths, torch.Tensor)
+                                 else lengths)]
+        rows = [None] * len(encs)
+        lin = [i for i, e in enumerate(encs) if e == "pcm16"]
+        comp = [i for i, e in enumerate(encs) if e != "pcm16"]
+        for idx in (lin, comp):
+            if not idx:
+                continue
+            if len(idx) == len(encs):
+                part, pl = y, lens
+            else:
+                sel = torch.tensor(idx, dtype=torch.long, device=y.device)
+                pl = [lens[i] for i in idx]
+                part = y.index_select(0, sel)[:, : max(pl, default=0)]
+            ps = [sil[i] for i in idx]
+            if idx is lin:
+                wire, wl = pcm16_rows(part, pl, ps)
+            else:
+                wire, wl = g711_rows(part, pl, ps, [encs[i] for i in idx])
+            wire = wire.cpu().numpy()
+            for r, i in enumerate(idx):
+                rows[i] = wire[r, : int(wl[r])]
+        return rows
+
     @torch.no_grad()
     def speak_batch_pcm(self, phonemes_batch: Sequence[str], prosody=None,
-                        silence_ms=None, sample_rate=None) -> List[PcmAudio]:
+                        silence_ms=None, sample_rate=None,
+                        encoding=None) -> List[PcmAudio]:
         """speak_batch whose results are wire-format int16: what
         `Audio.as_wave_bytes` gives for speak_batch's samples with
         `silence_ms` of silence merged on (per row or one value; rounded to
@@ -317,11 +361,18 @@ class VitsVoice(SonataModel):
         ops.resample_rows, ops.pcm16_rows, then ONE host copy of the int16
         batch per distinct rate: half the bytes of the float copy, and no
         per-row NumPy passes.  A CPU voice, or SONATA_DEVICE_PCM=0, converts
-        speak_batch's samples on the host: same bytes."""
+        speak_batch's samples on the host: same bytes.
+        `encoding` (one value or one per row: None, "pcm16", "ulaw",
+        "alaw") makes a row 8-bit G.711: audio.g711.encode of its int16.
+        On cuda the 8-bit rows of a rate are one ops.g711_rows launch with
+        per-row laws and one host copy of a quarter of the float bytes; a
+        batch that is all one kind costs the launches and copies of the
+        int16 path."""
         B = len(phonemes_batch)
         if silence_ms is None or isinstance(silence_ms, (int, float)):
             silence_ms = [silence_ms] * B
         assert len(silence_ms) == B, "one silence value per row"
+        encs = self._row_encodings(encoding, B)
         rates = self._row_rates(sample_rate, B)
         native = self.config.sample_rate
         converts = any(r != native for r in rates)
@@ -334,8 +385,8 @@ class VitsVoice(SonataModel):
             if converts:
                 kw["sample_rate"] = rates
             audios = self.speak_batch(phonemes_batch, **kw)
-            return [PcmAudio.from_audio(a, s) for a, s in zip(audios, sil)]
-        from ..ops import pcm16_rows
+            return [PcmAudio.from_audio(a, s, e)
+                    for a, s, e in zip(audios, sil, encs)]
 
         audio, audio_lengths, infer_ms = self._infer_batch(phonemes_batch)
         if prosody is not None:
@@ -345,20 +396,19 @@ class VitsVoice(SonataModel):
             out = [None] * B
             for rate, idx, y, out_lengths in self._resample_groups(
                     audio[:, 0, :], audio_lengths, rates):
-                pcm, pcm_lengths = pcm16_rows(y, out_lengths,
-                                              [sil[b] for b in idx])
-                pcm = pcm.cpu().numpy()
+                rows = self._wire_rows(y, out_lengths, [sil[b] for b in idx],
+                                       [encs[b] for b in idx])
                 rinfo = AudioInfo(sample_rate=rate)
                 for i, b in enumerate(idx):
-                    out[b] = PcmAudio(pcm[i, : int(pcm_lengths[i])], rinfo,
-                                      inference_ms=infer_ms / B)
+                    out[b] = PcmAudio(rows[i], rinfo,
+                                      inference_ms=infer_ms / B,
+                                      encoding=encs[b])
             return out
         # bf16 decoder output is read as it is (widening is exact)
-        pcm, out_lengths = pcm16_rows(audio[:, 0, :], audio_lengths, sil)
-        pcm = pcm.cpu().numpy()
+        rows = self._wire_rows(audio[:, 0, :], audio_lengths, sil, encs)
         info = self.audio_output_info()
-        return [PcmAudio(pcm[b, : int(out_lengths[b])], info,
-                         inference_ms=infer_ms / B) for b in range(B)]
+        return [PcmAudio(rows[b], info, inference_ms=infer_ms / B,
+                         encoding=encs[b]) for b in range(B)]
 
     # ------------------------------------------------------------------ #
     # streaming decode (encoder once, HiFi-GAN chunked)
@@ -731,14 +781,18 @@ class VitsVoice(SonataModel):
             return [self._tail_free.pop() for _ in range(n)]
 
     @torch.no_grad()
-    def _round_enqueue(self, states, pcm: bool, pins=None):
+    def _round_enqueue(self, states, pcm: bool, pins=None, encoding=None):
         """Take each live state's next chunk and enqueue gather -> decode ->
         seam (-> pcm) and the copy of the packed rows to the host.  Caller
         holds _infer_lock.  Returns what _round_collect needs, or None when
         no state is live."""
-        from ..ops import (gather_windows, pcm16_rows, prosody_stream_rows,
-                           resample_poly_stream_rows, stream_seam_rows)
+        from ..ops import (g711_rows, gather_windows, pcm16_rows,
+                           prosody_stream_rows, resample_poly_stream_rows,
+                           stream_seam_rows)
 
+        laws = self._round_laws(states, encoding)
+        if laws is not None:
+            laws = [w for s, w in zip(states, laws) if not s.done]
         live = [s for s in states if not s.done]
         if not live:
             return None
@@ -795,7 +849,9 @@ class VitsVoice(SonataModel):
                      and s.resample.rate_out == rate else None for s in live],
                     [s.slot for s in live], st,
                     last=[sp.is_last for sp in specs])
-            if pcm:
+            if laws is not None:
+                out, _ = g711_rows(out, out_len, law=laws)
+            elif pcm:
                 out, _ = pcm16_rows(out, out_len)
         finished = []
         for s, sp, e in zip(live, specs, ext):
@@ -826,6 +882,19 @@ class VitsVoice(SonataModel):
             return self._engine.decode(z_c, m_c, g, lens_t)
         return self.net.decode(z_c, m_c, g, lengths=lens_t)
 
+    @classmethod
+    def _round_laws(cls, states, encoding):
+        """One G.711 law per state, or None for a round that is not 8-bit.
+        A round has one output dtype: its rows share one host copy."""
+        encs = cls._row_encodings(encoding, len(states))
+        if all(e == "pcm16" for e in encs):
+            return None
+        if any(e == "pcm16" for e in encs):
+            raise ValueError(
+                "a stream round is all pcm16 or all G.711: its rows share "
+                "one host copy")
+        return encs
+
     def _round_pins(self):
         if not hasattr(self, "_round_pin_bufs"):
             self._round_pin_bufs = _PinnedPair()
@@ -841,7 +910,7 @@ class VitsVoice(SonataModel):
         return [(s, rows[r, : out_len[r]].copy())
                 for r, s in enumerate(live)]
 
-    def stream_round(self, states, pcm: bool = False):
+    def stream_round(self, states, pcm: bool = False, encoding=None):
         """Advance every live state by one chunk in ONE decode: gather the
         latent windows, decode them as a ragged batch, trim and crossfade
         per stream on the device, copy the packed rows to the host once.
@@ -849,11 +918,15 @@ class VitsVoice(SonataModel):
         chunks, or int16 (ops.pcm16_rows of the float chunk) with pcm=True.
         A state opened with a prosody triple has it applied before the copy
         (and before the PCM conversion); its chunk may then be empty.
+        `encoding` ("ulaw" / "alaw", one value or one per state) makes the
+        chunks uint8 G.711 instead: ops.g711_rows of the float chunk, peak-
+        normalised per chunk as the int16 chunks are.  Both laws share a
+        round; G.711 and pcm16 states do not (ValueError).
         A state whose chunk was its last is finished (state.done).  Holds
         the inference lock for the round only, and always decodes eagerly
         (R and the window length change from round to round)."""
         with self._infer_lock:
-            pending = self._round_enqueue(states, pcm)
+            pending = self._round_enqueue(states, pcm, encoding=encoding)
             if pending is None:
                 return []
             # collected under the lock: the pinned pair belongs to the voice
@@ -862,7 +935,7 @@ class VitsVoice(SonataModel):
     def stream_synthesis_batch(self, phonemes_batch: Sequence[str],
                                chunk_size=45, chunk_padding: int = 3,
                                pcm: bool = False, prosody=None,
-                               sample_rate=None):
+                               sample_rate=None, encoding=None):
         """stream_synthesis for a list of sentences at once: yields (index,
         chunk) with, per index, the chunk boundaries, total length and seams
         of stream_synthesis.  One encoder call, then one decode per round
@@ -875,13 +948,15 @@ class VitsVoice(SonataModel):
         may be empty (every live stream still yields one per round).
         `sample_rate` is stream_open's too: an index's chunks then
         concatenate to ops.resample_rows of its stream without a rate, and
-        a chunk may be empty."""
+        a chunk may be empty.
+        `encoding` is stream_round's, one value or one per sentence."""
+        self._round_laws(phonemes_batch, encoding)  # checked before opening
         states = self.stream_open(phonemes_batch, chunk_size, chunk_padding,
                                   prosody=prosody, sample_rate=sample_rate)
         pins = _PinnedPair() if self.device.type == "cuda" else None
         try:
             with self._infer_lock:
-                pending = self._round_enqueue(states, pcm, pins)
+                pending = self._round_enqueue(states, pcm, pins, encoding)
             pipelined = self.device.type == "cuda"
             first = True
             while pending is not None:
@@ -889,12 +964,12 @@ class VitsVoice(SonataModel):
                 nxt = None
                 if ahead:
                     with self._infer_lock:
-                        nxt = self._round_enqueue(states, pcm, pins)
+                        nxt = self._round_enqueue(states, pcm, pins, encoding)
                 for s, chunk in self._round_collect(pending):
                     yield s.index, chunk
                 if not ahead:
                     with self._infer_lock:
-                        nxt = self._round_enqueue(states, pcm, pins)
+                        nxt = self._round_enqueue(states, pcm, pins, encoding)
                 first = False
                 pending = nxt
         finally:

@@ -75,6 +75,7 @@ from .functional import (  # noqa: F401,E402
     wsola_rows,
     apply_prosody_rows,
     pcm16_rows,
+    g711_rows,
     resample_rows,
     gather_windows,
     stream_seam_rows,

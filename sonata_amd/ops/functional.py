@@ -910,6 +910,59 @@ def pcm16_rows(x: torch.Tensor, lengths, silence=None,
     return pcm, out_lengths
 
 
+def _per_row_law(law, B: int):
+    from ..audio.g711 import check_law
+
+    if isinstance(law, str):
+        return [check_law(law)] * B
+    out = [check_law(v) for v in law]
+    assert len(out) == B, "one law per row"
+    return out
+
+
+def g711_rows(x: torch.Tensor, lengths, silence=None, law="ulaw",
+              peak_normalize: bool = True):
+    """G.711 codes of x [B, N] (f32 or bf16) rows of lengths[b] samples:
+    audio.g711.encode of what pcm16_rows gives for the row, without the
+    int16 in between.  `law` is "ulaw" or "alaw", one name or one per row;
+    `silence` (samples, per row or one int) is appended as the row's code of
+    sample 0.  Returns (codes uint8 [B, N_out], out_lengths) with
+    out_lengths[b] = lengths[b] + silence[b] and N_out = max(out_lengths)
+    rounded up to a multiple of 16 (aligned rows); columns past lengths[b]
+    are g711.ZERO[law[b]]."""
+    from ..audio import g711
+
+    B = x.shape[0]
+    lens = _row_lengths(lengths, B)
+    assert all(0 <= n <= x.shape[1] for n in lens), "length outside the row"
+    sil = _per_row_int(silence, B)
+    assert all(s >= 0 for s in sil), "negative silence"
+    laws = _per_row_law(law, B)
+    out = [n + s for n, s in zip(lens, sil)]
+    n_out = _round_up(max(out, default=0), 16)
+    out_lengths = torch.tensor(out, dtype=torch.long)
+    if not use_hip(x):
+        import numpy as np
+
+        from ..audio.samples import to_i16
+
+        xn = x.detach().float().cpu().numpy()
+        y = np.empty((B, n_out), dtype=np.uint8)
+        for b in range(B):
+            y[b, lens[b]:] = g711.ZERO[laws[b]]
+            y[b, : lens[b]] = g711.encode(
+                to_i16(xn[b, : lens[b]], peak_normalize), laws[b])
+        return torch.from_numpy(y).to(x.device), out_lengths
+    ext = hip_ext(required=True)
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        x = x.contiguous()
+    # lengths and laws (checked above: 0 or 1) go up in one copy
+    par = _i32([lens, [g711.LAWS.index(v) for v in laws]], x.device)
+    codes, _peaks = ext.g711_rows(x, par[0], par[1], n_out,
+                                  bool(peak_normalize))
+    return codes, out_lengths
+
+
 # --------------------------------------------------------------------------- #
 # batched output sample-rate conversion (csrc/resample.hip): the polyphase
 # FIR of audio.resample on [B, N] f32 / bf16 rows.  The CPU path calls

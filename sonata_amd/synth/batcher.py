@@ -18,6 +18,7 @@ import threading
 from concurrent.futures import Future
 from typing import List, Optional, Sequence
 
+from ..audio.g711 import check_encoding
 from ..audio.resample import check_rate, is_identity, resample_poly
 from ..audio.samples import silence_samples
 from ..core import Audio, AudioInfo, PcmAudio, SonataModel
@@ -30,7 +31,8 @@ class DynamicBatcher:
         self.max_batch = max_batch
         self.max_wait = max_wait_ms / 1000.0
         # items: (phonemes, future, prosody triple or None, pcm,
-        #         silence_ms or None, output sample rate or None)
+        #         silence_ms or None, output sample rate or None,
+        #         wire encoding)
         self._q: "queue.Queue[Optional[tuple]]" = queue.Queue()
         self._worker = threading.Thread(target=self._run, daemon=True,
                                         name="sonata_batcher")
@@ -41,7 +43,8 @@ class DynamicBatcher:
                prosody: Optional[Sequence[float]] = None,
                pcm: bool = False,
                silence_ms: Optional[float] = None,
-               sample_rate: Optional[int] = None) -> "Future[Audio]":
+               sample_rate: Optional[int] = None,
+               encoding: Optional[str] = None) -> "Future[Audio]":
         """Queue one sentence; the future resolves with its Audio.
         `prosody`: optional (speed, volume, pitch) applied to this request's
         row by the model (speak_batch(prosody=...)); rows of one batch may
@@ -53,10 +56,16 @@ class DynamicBatcher:
         `sample_rate`: optional output rate of this request's row; it rides
         with the request as the prosody triple does, and requests with
         different rates still share one speak_batch* call.  A rate the
-        filter does not serve raises ValueError here."""
+        filter does not serve raises ValueError here.
+        `encoding`: optional wire encoding of a pcm request ("pcm16",
+        "ulaw", "alaw"); it rides with the request too, and requests with
+        different encodings still share one speak_batch_pcm.  Anything else
+        raises ValueError here."""
         if self._closed:
             raise RuntimeError("batcher closed")
         assert pcm or not silence_ms, "silence_ms rides with pcm requests"
+        encoding = check_encoding(encoding)
+        assert pcm or encoding == "pcm16", "encoding rides with pcm requests"
         if sample_rate is not None:
             native = self.model.audio_output_info().sample_rate
             if is_identity(native, sample_rate):
@@ -66,7 +75,8 @@ class DynamicBatcher:
                 sample_rate = int(sample_rate)
         f: "Future[Audio]" = Future()
         self._q.put((phonemes, f, tuple(prosody) if prosody is not None
-                     else None, bool(pcm), silence_ms, sample_rate))
+                     else None, bool(pcm), silence_ms, sample_rate,
+                     encoding))
         return f
 
     def synthesize(self, phonemes: str) -> Audio:
@@ -127,6 +137,9 @@ class DynamicBatcher:
         try:
             if all(it[3] for it in bucket) and not host_rate and getattr(
                     self.model, "supports_device_pcm", False):
+                encs = [it[6] for it in bucket]
+                if any(e != "pcm16" for e in encs):
+                    kw["encoding"] = encs
                 audios = self.model.speak_batch_pcm(
                     phonemes, silence_ms=[it[4] for it in bucket], **kw)
             else:
@@ -134,7 +147,7 @@ class DynamicBatcher:
                 if host_rate:
                     audios = [self._host_rate(a, r)
                               for a, r in zip(audios, rates)]
-                audios = [self._host_pcm(a, it[4]) if it[3] else a
+                audios = [self._host_pcm(a, it[4], it[6]) if it[3] else a
                           for it, a in zip(bucket, audios)]
             for it, audio in zip(bucket, audios):
                 it[1].set_result(audio)
@@ -152,10 +165,11 @@ class DynamicBatcher:
                      AudioInfo(sample_rate=rate), audio.inference_ms)
 
     @staticmethod
-    def _host_pcm(audio: Audio, silence_ms: Optional[float]) -> PcmAudio:
+    def _host_pcm(audio: Audio, silence_ms: Optional[float],
+                  encoding: str = "pcm16") -> PcmAudio:
         sil = (silence_samples(silence_ms, audio.info.sample_rate)
                if silence_ms else 0)
-        return PcmAudio.from_audio(audio, sil)
+        return PcmAudio.from_audio(audio, sil, encoding)
 
 
 class _StreamHandle:
@@ -163,11 +177,12 @@ class _StreamHandle:
     once opened, its model state."""
 
     __slots__ = ("phonemes", "chunk_size", "chunk_padding", "pcm", "q",
-                 "cancelled", "state", "prosody", "sample_rate")
+                 "cancelled", "state", "prosody", "sample_rate", "encoding")
 
     def __init__(self, phonemes, chunk_size, chunk_padding, pcm,
-                 prosody=None, sample_rate=None):
+                 prosody=None, sample_rate=None, encoding="pcm16"):
         self.phonemes = phonemes
+        self.encoding = encoding
         self.prosody = tuple(prosody) if prosody is not None else None
         self.sample_rate = sample_rate
         self.chunk_size = int(chunk_size)
@@ -176,6 +191,14 @@ class _StreamHandle:
         self.q: "queue.Queue" = queue.Queue()
         self.cancelled = False
         self.state = None
+
+    @property
+    def kind(self) -> int:
+        """Output dtype of the stream's chunks: 0 float32, 1 int16, 2 uint8
+        (G.711, either law)."""
+        if self.encoding != "pcm16":
+            return 2
+        return 1 if self.pcm else 0
 
     def window(self) -> int:
         spec = self.state.next_spec
@@ -242,7 +265,8 @@ class StreamBatcher:
 
     def open(self, phonemes: str, chunk_size: int = 45,
              chunk_padding: int = 3, pcm: bool = False, prosody=None,
-             sample_rate: Optional[int] = None):
+             sample_rate: Optional[int] = None,
+             encoding: Optional[str] = None):
         """Start one stream; returns the iterator of its chunks (float32
         arrays, or int16 with pcm=True), those model.stream_synthesis
         yields for the same arguments.
@@ -256,9 +280,14 @@ class StreamBatcher:
         streams of one round may each carry their own.  The chunks then
         concatenate to the conversion of the whole stream, and rounds in
         which the filter emits nothing yield no chunk.  A rate the filter
-        does not serve raises ValueError here."""
+        does not serve raises ValueError here.
+        `encoding`: "ulaw" or "alaw" makes the chunks uint8 G.711 codes
+        (model.stream_round(encoding=...): the codes of the int16 chunks
+        pcm=True gives); mu-law and A-law streams share a round.  None or
+        "pcm16" changes nothing; anything else raises ValueError here."""
         if self._closed:
             raise RuntimeError("stream batcher closed")
+        encoding = check_encoding(encoding)
         if sample_rate is not None:
             native = self.model.audio_output_info().sample_rate
             if is_identity(native, sample_rate):
@@ -267,7 +296,7 @@ class StreamBatcher:
                 check_rate(native, sample_rate)
                 sample_rate = int(sample_rate)
         h = _StreamHandle(phonemes, chunk_size, chunk_padding, pcm, prosody,
-                          sample_rate)
+                          sample_rate, encoding)
         self._q.put(h)
         return _StreamIter(h)
 
@@ -339,10 +368,11 @@ class StreamBatcher:
         """Shortest windows first, cut where the next window is more than
         twice the bucket's shortest (DynamicBatcher._flush's rule on window
         length): a newcomer's 45-frame chunk neither pays for nor waits
-        behind a 225-frame one.  Float and PCM streams decode apart."""
+        behind a 225-frame one.  Float, int16 and 8-bit streams decode
+        apart (a round has one output dtype); both laws share a round."""
         out = []
-        for pcm in (False, True):
-            part = sorted((h for h in live if h.pcm == pcm),
+        for kind in (0, 1, 2):
+            part = sorted((h for h in live if h.kind == kind),
                           key=_StreamHandle.window)
             start = 0
             for i in range(1, len(part) + 1):
@@ -356,8 +386,10 @@ class StreamBatcher:
     def _round(self, bucket: List[_StreamHandle]) -> List[_StreamHandle]:
         """One decode for the bucket; returns the handles still live."""
         try:
+            kw = ({"encoding": [h.encoding for h in bucket]}
+                  if bucket[0].kind == 2 else {})
             chunks = self.model.stream_round([h.state for h in bucket],
-                                             pcm=bucket[0].pcm)
+                                             pcm=bucket[0].pcm, **kw)
         except BaseException as e:  # noqa: BLE001 - reaches the callers
             self._fail(bucket, e)
             return []

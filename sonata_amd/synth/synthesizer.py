@@ -26,8 +26,11 @@ import numpy as np
 from ..audio.prosody import apply_prosody
 from ..audio.resample import (StreamResampler, check_rate, is_identity,
                               resample_poly)
-from ..audio.samples import generate_silence, merge, silence_samples
-from ..audio.wav import write_wav_file
+from ..audio.g711 import check_encoding
+from ..audio.g711 import encode as g711_encode
+from ..audio.samples import (generate_silence, merge, silence_samples,
+                             to_i16)
+from ..audio.wav import write_wav_file, write_wav_file_g711
 from ..core import Audio, AudioInfo, PcmAudio, SonataModel
 
 # percent(0-100) -> parameter ranges (reference synth/src/lib.rs:13-15)
@@ -74,13 +77,18 @@ class AudioOutputConfig:
     """Prosody knobs in percent (0-100) + appended silence, mirroring the
     reference AudioOutputConfig (synth/src/lib.rs:28-117).  `sample_rate`
     (Hz, not percent) asks for the result at another rate than the voice's
-    own; it is no part of `is_noop`, which speaks of prosody alone."""
+    own; it is no part of `is_noop`, which speaks of prosody alone.
+    `encoding` (None, "pcm16", "ulaw" or "alaw") chooses the wire format of
+    PcmAudio results and written files: 16-bit linear PCM, or 8-bit G.711
+    (audio.g711.encode of that PCM).  Float results never change, and it
+    is no part of `is_noop` either."""
 
     rate: Optional[float] = None
     volume: Optional[float] = None
     pitch: Optional[float] = None
     appended_silence_ms: Optional[float] = None
     sample_rate: Optional[int] = None
+    encoding: Optional[str] = None
 
     def prosody_triple(self):
         """(speed, volume, pitch) as parameters (not percent) — what `apply`
@@ -168,6 +176,13 @@ class SonataSpeechSynthesizer:
         check_rate(native, cfg.sample_rate)
         return int(cfg.sample_rate)
 
+    @staticmethod
+    def output_encoding(cfg: Optional[AudioOutputConfig]) -> str:
+        """The wire encoding `cfg` asks for: "pcm16" (also for None),
+        "ulaw" or "alaw".  Raises ValueError for anything else."""
+        return check_encoding(getattr(cfg, "encoding", None)
+                              if cfg is not None else None)
+
     def device_rate(self, cfg: Optional[AudioOutputConfig]) -> bool:
         """True when the conversion to cfg's rate runs inside speak_batch*:
         the model offers it and lives on cuda, and prosody, which comes
@@ -243,6 +258,7 @@ class SonataSpeechSynthesizer:
         host_prosody = (cfg is not None and not cfg.is_noop
                         and not self.device_prosody(cfg))
         rate = self.output_rate(cfg)
+        enc = self.output_encoding(cfg)
         if rate is not None and not self.device_rate(cfg):
             # the conversion runs on the host, so the float path is kept up
             # to it (device prosody first, where it is on)
@@ -259,12 +275,14 @@ class SonataSpeechSynthesizer:
             triple = (cfg.prosody_triple()
                       if cfg is not None and not cfg.is_noop else None)
             kw = {"sample_rate": rate} if rate is not None else {}
+            if enc != "pcm16":
+                kw["encoding"] = enc
             return self.model.speak_batch_pcm(
                 sentences,
                 prosody=[triple] * len(sentences) if triple else None,
                 silence_ms=cfg.appended_silence_ms if cfg else None, **kw)
         if rate is not None:
-            return [PcmAudio.from_audio(a)
+            return [PcmAudio.from_audio(a, encoding=enc)
                     for a in self._speak_rate(sentences, cfg, rate)]
         batch = self.model.speak_batch(sentences)
         return [self.to_pcm(a, cfg) for a in batch]
@@ -274,7 +292,8 @@ class SonataSpeechSynthesizer:
                rate: Optional[int] = None) -> PcmAudio:
         """Host finish of one float result: prosody unless done, the
         conversion to `rate` when one is given, then the int16 conversion
-        with cfg's silence appended (counted at the result's rate)."""
+        with cfg's silence appended (counted at the result's rate), then
+        cfg's G.711 encoding when it names one."""
         if cfg is not None and not cfg.is_noop and not prosody_done:
             audio = Audio(cfg.apply(audio.samples, audio.info.sample_rate),
                           audio.info, audio.inference_ms)
@@ -282,7 +301,7 @@ class SonataSpeechSynthesizer:
         sil = (silence_samples(cfg.appended_silence_ms,
                                audio.info.sample_rate)
                if cfg is not None and cfg.appended_silence_ms else 0)
-        return PcmAudio.from_audio(audio, sil)
+        return PcmAudio.from_audio(audio, sil, self.output_encoding(cfg))
 
     # ------------------------------------------------------------------ #
     def synthesize_lazy(
@@ -294,6 +313,7 @@ class SonataSpeechSynthesizer:
         `pcm=True` yields PcmAudio (int16, converted on the device when the
         model can) instead of float Audio; the wire bytes are the same."""
         rate = self.output_rate(output_config)
+        self.output_encoding(output_config)
         phonemes = self.model.phonemize_text(text)
         for sent in phonemes:
             if pcm:
@@ -315,6 +335,7 @@ class SonataSpeechSynthesizer:
         out per-sentence rayon tasks (synth/src/lib.rs:316-320); here the
         model's true padded batch path does the fan-out on-device.
         `pcm=True` yields PcmAudio, as in synthesize_lazy."""
+        self.output_encoding(output_config)
         phonemes = self.model.phonemize_text(text)
         if len(phonemes) == 0:
             return iter(())
@@ -451,7 +472,10 @@ class SonataSpeechSynthesizer:
         output_config: Optional[AudioOutputConfig] = None,
     ) -> Audio:
         """Collect parallel synthesis into one WAV (reference
-        synthesize_to_file, synth/src/lib.rs:170-198)."""
+        synthesize_to_file, synth/src/lib.rs:170-198).  With a G.711
+        encoding in the output config the file holds the codes of the int16
+        it would hold otherwise."""
+        enc = self.output_encoding(output_config)
         pieces: List[np.ndarray] = []
         info = self.model.audio_output_info()
         inference_ms = 0.0
@@ -462,7 +486,11 @@ class SonataSpeechSynthesizer:
         samples = (
             np.concatenate(pieces) if pieces else np.zeros(0, dtype=np.float32)
         )
-        write_wav_file(path, samples, info.sample_rate)
+        if enc != "pcm16":
+            write_wav_file_g711(path, g711_encode(to_i16(samples), enc),
+                                info.sample_rate, enc)
+        else:
+            write_wav_file(path, samples, info.sample_rate)
         return Audio(samples, info, inference_ms)
 
     # delegation (reference re-implements SonataModel by delegation,
