@@ -508,6 +508,40 @@ static void launch_conv_mfma(const bf16* x, const bf16* w, const float* bias,
 #undef LAUNCH
 }
 
+// Tile height the launchers pick for Cout; the permuted weights are padded
+// to a multiple of it (launch_conv_mfma and the merged transposed kernel
+// use the same classes).
+static inline long conv_bm(long Cout) {
+  return Cout >= 128 ? 128 : (Cout >= 64 ? 64 : 32);
+}
+
+// Host-side argument checks shared by the two bindings.  Everything the
+// kernels index by is validated here, before any launch.
+static const float* checked_bias(const c10::optional<torch::Tensor>& bias,
+                                 const torch::Tensor& x, long Cout,
+                                 torch::Tensor& bias_f, const char* op) {
+  if (!bias.has_value()) return nullptr;
+  TORCH_CHECK(bias->dim() == 1 && bias->size(0) == Cout, op,
+              ": bias must be [Cout=", Cout, "], got ", bias->sizes());
+  TORCH_CHECK(bias->device() == x.device(), op,
+              ": bias must be on x's device");
+  bias_f = bias->scalar_type() == at::kFloat
+               ? bias->contiguous()
+               : bias->to(at::kFloat).contiguous();
+  return bias_f.data_ptr<float>();
+}
+
+static void check_padded_dims(long CoutP, long CinP, long Cout, long Cin,
+                              const char* op) {
+  const long bm = conv_bm(Cout);
+  TORCH_CHECK(CoutP >= Cout && CoutP % bm == 0, op, ": permuted weight has "
+              "CoutP=", CoutP, "; need a multiple of the tile height ", bm,
+              " that is >= Cout=", Cout);
+  TORCH_CHECK(CinP >= Cin && CinP % BK == 0, op, ": permuted weight has "
+              "CinP=", CinP, "; need a multiple of ", BK, " that is >= Cin=",
+              Cin);
+}
+
 torch::Tensor conv1d_fused(torch::Tensor x, torch::Tensor w_perm,
                            c10::optional<torch::Tensor> bias, long Cout,
                            long k, long stride, long padding, long dilation,
@@ -515,30 +549,72 @@ torch::Tensor conv1d_fused(torch::Tensor x, torch::Tensor w_perm,
                            double post_slope,
                            c10::optional<torch::Tensor> residual) {
   // w_perm: [k][CoutP][CinP] bf16 (pre-permuted+padded) for the MFMA path
-  //         or the raw [Cout][Cin/g][k] tensor for the fallback path.
-  TORCH_CHECK(x.dim() == 3 && x.is_cuda() && x.is_contiguous());
+  //         or the raw [Cout][Cin/g][k] tensor, in x's dtype, for the
+  //         fallback path.  The layout is decided by the full shape; when
+  //         the arguments take the MFMA path and a shape reads both ways
+  //         (k == Cout == Cin, a multiple of 32) it is the permuted one.
+  static const char* op = "conv1d_fused";
+  TORCH_CHECK(x.dim() == 3 && x.is_cuda() && x.is_contiguous(), op,
+              ": x must be a contiguous [B,Cin,T] device tensor");
+  TORCH_CHECK(Cout >= 1 && k >= 1 && stride >= 1 && dilation >= 1 &&
+              padding >= 0 && groups >= 1, op, ": bad conv arguments");
+  TORCH_CHECK(act_mode >= ACT_NONE && act_mode <= ACT_TANH, op,
+              ": act_mode must be 0 (none), 1 (lrelu) or 2 (tanh)");
   const long B = x.size(0), Cin = x.size(1), Tin = x.size(2);
+  TORCH_CHECK(Cin % groups == 0 && Cout % groups == 0, op, ": Cin=", Cin,
+              " and Cout=", Cout, " must be divisible by groups=", groups);
   const long Tout = conv_out_len(Tin, k, stride, padding, dilation);
-  auto out = torch::empty({B, Cout, Tout}, x.options());
-  if (out.numel() == 0) return out;
-  torch::Tensor bias_f;
-  const float* bias_p = nullptr;
-  if (bias.has_value()) {
-    bias_f = bias->scalar_type() == at::kFloat
-                 ? *bias
-                 : bias->to(at::kFloat).contiguous();
-    bias_p = bias_f.data_ptr<float>();
-  }
+  TORCH_CHECK(Tin + 2 * padding >= dilation * (k - 1) + 1 && Tout > 0, op,
+              ": empty output (Tin=", Tin, ", k=", k, ", dilation=", dilation,
+              ", padding=", padding, ")");
   const bool mfma_ok = x.scalar_type() == at::kBFloat16 && groups == 1 &&
-                       stride == 1 && w_perm.dim() == 3 &&
-                       w_perm.size(0) == k &&
-                       (k - 1) * dilation <= 64 /* HALO_MAX */;
+                       stride == 1 && (k - 1) * dilation <= HALO_MAX;
+  TORCH_CHECK(w_perm.dim() == 3, op, ": weight must be 3-D, got ",
+              w_perm.sizes());
+  TORCH_CHECK(w_perm.device() == x.device(), op,
+              ": weight must be on x's device");
+  TORCH_CHECK(w_perm.is_contiguous(), op, ": weight must be contiguous");
+  const bool raw_shape = w_perm.size(0) == Cout &&
+                         w_perm.size(1) == Cin / groups &&
+                         w_perm.size(2) == k;
+  const bool padded_ok =
+      w_perm.size(0) == k && w_perm.size(1) >= Cout &&
+      w_perm.size(1) % conv_bm(Cout) == 0 && w_perm.size(2) >= Cin &&
+      w_perm.size(2) % BK == 0;
+  // MFMA arguments: a [k,.,.] tensor is the permuted weight (and must then
+  // be padded correctly) unless it is exactly the raw shape and not a
+  // valid padded one.
+  const bool use_mfma =
+      mfma_ok && w_perm.size(0) == k && (padded_ok || !raw_shape);
+  if (use_mfma) {
+    TORCH_CHECK(w_perm.scalar_type() == at::kBFloat16, op,
+                ": permuted weight must be bf16");
+    check_padded_dims(w_perm.size(1), w_perm.size(2), Cout, Cin, op);
+  } else {
+    TORCH_CHECK(raw_shape || mfma_ok || !padded_ok, op,
+                ": permuted [k,CoutP,CinP] weight offered to the fallback "
+                "path (needs bf16, groups 1, stride 1 and (k-1)*dilation <= ",
+                HALO_MAX, "); pass the raw [Cout,Cin/groups,k] weight");
+    TORCH_CHECK(raw_shape, op, ": weight ", w_perm.sizes(),
+                " is neither the raw [", Cout, ",", Cin / groups, ",", k,
+                "] nor the permuted [k,CoutP,CinP] shape");
+    TORCH_CHECK(w_perm.scalar_type() == x.scalar_type(), op,
+                ": raw weight must have x's dtype");
+  }
+  torch::Tensor bias_f;
+  const float* bias_p = checked_bias(bias, x, Cout, bias_f, op);
+  auto out = torch::empty({B, Cout, Tout}, x.options());
   const bf16* res_p = nullptr;
   if (residual.has_value()) {
-    TORCH_CHECK(residual->sizes() == out.sizes() && residual->is_contiguous());
+    TORCH_CHECK(residual->sizes() == out.sizes() && residual->is_contiguous(),
+                op, ": residual must be a contiguous [B,Cout,Tout] tensor");
+    TORCH_CHECK(residual->scalar_type() == x.scalar_type() &&
+                residual->device() == x.device(), op,
+                ": residual must have x's dtype and device");
     res_p = (const bf16*)residual->data_ptr();
   }
-  if (mfma_ok) {
+  if (out.numel() == 0) return out;
+  if (use_mfma) {
     const int CoutP = w_perm.size(1), CinP = w_perm.size(2);
     launch_conv_mfma((const bf16*)x.data_ptr(),
                      (const bf16*)w_perm.data_ptr(), bias_p,
@@ -568,22 +644,49 @@ torch::Tensor convtranspose1d_fused(torch::Tensor x, torch::Tensor w_perm,
                                     c10::optional<torch::Tensor> bias,
                                     long Cout, long k, long stride,
                                     long padding, double pre_lrelu) {
-  // w_perm (MFMA): [s][kr_max][CoutP][CinP]; fallback: raw [Cin][Cout][k].
-  TORCH_CHECK(x.dim() == 3 && x.is_cuda() && x.is_contiguous());
+  // w_perm (MFMA): [s][kr_max][CoutP][CinP] bf16; fallback: raw
+  // [Cin][Cout][k] in x's dtype.
+  static const char* op = "convtranspose1d_fused";
+  TORCH_CHECK(x.dim() == 3 && x.is_cuda() && x.is_contiguous(), op,
+              ": x must be a contiguous [B,Cin,T] device tensor");
+  TORCH_CHECK(Cout >= 1 && k >= 1 && stride >= 1 && padding >= 0, op,
+              ": bad conv arguments");
   const long B = x.size(0), Cin = x.size(1), Tin = x.size(2);
   const long Tout = (Tin - 1) * stride - 2 * padding + k;
+  TORCH_CHECK(Tin >= 1 && Tout > 0, op, ": empty output (Tin=", Tin, ", k=",
+              k, ", stride=", stride, ", padding=", padding, ")");
+  TORCH_CHECK(w_perm.dim() == 3 || w_perm.dim() == 4, op,
+              ": weight must be the raw [Cin,Cout,k] or the permuted "
+              "[s,kr_max,CoutP,CinP] tensor, got ", w_perm.sizes());
+  TORCH_CHECK(w_perm.device() == x.device(), op,
+              ": weight must be on x's device");
+  TORCH_CHECK(w_perm.is_contiguous(), op, ": weight must be contiguous");
+  const bool mfma_ok = w_perm.dim() == 4;
+  if (mfma_ok) {
+    TORCH_CHECK(x.scalar_type() == at::kBFloat16, op,
+                ": permuted weight offered to the fallback path (x is not "
+                "bf16); pass the raw [Cin,Cout,k] weight");
+    TORCH_CHECK(w_perm.scalar_type() == at::kBFloat16, op,
+                ": permuted weight must be bf16");
+    const long kr = (k + stride - 1) / stride;
+    TORCH_CHECK(w_perm.size(0) == stride, op, ": permuted weight has ",
+                w_perm.size(0), " phases for stride ", stride);
+    TORCH_CHECK(w_perm.size(1) == kr, op, ": permuted weight has kr_max=",
+                w_perm.size(1), "; k=", k, " and stride=", stride, " give ",
+                kr);
+    TORCH_CHECK(kr - 1 <= HALO_MAX, op, ": too many taps per phase");
+    check_padded_dims(w_perm.size(2), w_perm.size(3), Cout, Cin, op);
+  } else {
+    TORCH_CHECK(w_perm.size(0) == Cin && w_perm.size(1) == Cout &&
+                w_perm.size(2) == k, op, ": weight ", w_perm.sizes(),
+                " is not the raw [", Cin, ",", Cout, ",", k, "] shape");
+    TORCH_CHECK(w_perm.scalar_type() == x.scalar_type(), op,
+                ": raw weight must have x's dtype");
+  }
+  torch::Tensor bias_f;
+  const float* bias_p = checked_bias(bias, x, Cout, bias_f, op);
   auto out = torch::empty({B, Cout, Tout}, x.options());
   if (out.numel() == 0) return out;
-  torch::Tensor bias_f;
-  const float* bias_p = nullptr;
-  if (bias.has_value()) {
-    bias_f = bias->scalar_type() == at::kFloat
-                 ? *bias
-                 : bias->to(at::kFloat).contiguous();
-    bias_p = bias_f.data_ptr<float>();
-  }
-  const bool mfma_ok =
-      x.scalar_type() == at::kBFloat16 && w_perm.dim() == 4;
   if (mfma_ok) {
     const int kr_max = w_perm.size(1);
     const int CoutP = w_perm.size(2), CinP = w_perm.size(3);
@@ -592,7 +695,7 @@ torch::Tensor convtranspose1d_fused(torch::Tensor x, torch::Tensor w_perm,
     hipStream_t st = cur_stream2();
     const bf16* xp = (const bf16*)x.data_ptr();
     const bf16* wp = (const bf16*)w_perm.data_ptr();
-    bf16* op = (bf16*)out.data_ptr();
+    bf16* outp = (bf16*)out.data_ptr();
     // merged kernel needs WM = BM/WGM >= 16 (MT >= 1); BM=32 with the
     // fixed 4x2 wave grid gives MT=0 -> Cout<64 uses the generic path.
     bool merged = (k == 2 * stride) && kr_max == 2 &&
@@ -600,7 +703,7 @@ torch::Tensor convtranspose1d_fused(torch::Tensor x, torch::Tensor w_perm,
 #define LAUNCH_M(BM, WGM, WGN, S)                                           \
   hipLaunchKernelGGL((convt1d_merged_kernel<BM, WGM, WGN, S, 2>),           \
                      dim3(ceil_div(Vn, 32), ceil_div(Cout, BM), B),         \
-                     dim3(512), 0, st, xp, wp, bias_p, op, Cin, CinP,       \
+                     dim3(512), 0, st, xp, wp, bias_p, outp, Cin, CinP,       \
                      Cout, CoutP, Tin, Tout, (int)padding, Vn, pre)
     if (merged && stride == 8) {
       if (Cout >= 128) LAUNCH_M(128, 4, 2, 8);
@@ -612,7 +715,7 @@ torch::Tensor convtranspose1d_fused(torch::Tensor x, torch::Tensor w_perm,
       else LAUNCH_M(64, 4, 2, 2); /* unreachable: Cout>=64 guard */
     } else {
       // generic: all phase GEMMs in one launch (phase folded into grid.y)
-      launch_conv_mfma(xp, wp, bias_p, op, nullptr, B, Cin, CinP, Cout,
+      launch_conv_mfma(xp, wp, bias_p, outp, nullptr, B, Cin, CinP, Cout,
                        CoutP, Tin, Tout, kr_max, -1, 0, Vn, stride, 0,
                        pre, ACT_NONE, 0.f, st,
                        (int)stride, (int)k, (int)padding, kr_max);

@@ -129,6 +129,20 @@ def _round_up(v: int, m: int) -> int:
     return (v + m - 1) // m * m
 
 
+# Widest halo (k-1)*dilation conv1d_mfma_kernel stages beside a time tile
+# (HALO_MAX in csrc/conv1d.hip).  conv1d_fused sends anything wider to the
+# naive kernel, which reads the raw [Cout, Cin/groups, k] weight.
+CONV_MFMA_HALO_MAX = 64
+
+
+def _conv_takes_mfma(x: torch.Tensor, k: int, stride: int, dilation: int,
+                     groups: int) -> bool:
+    """True when conv1d_fused will run the MFMA kernel for these arguments,
+    i.e. when it expects the `_conv_weight_mfma` layout."""
+    return (x.dtype == torch.bfloat16 and groups == 1 and stride == 1
+            and (k - 1) * dilation <= CONV_MFMA_HALO_MAX)
+
+
 def _conv_weight_mfma(weight: torch.Tensor) -> torch.Tensor:
     """Cache the MFMA layout of a conv weight: [Cout,Cin,k] ->
     [k, CoutP, CinP] bf16, Cout padded to the tile height, Cin to 32.
@@ -219,10 +233,9 @@ def leaky_conv1d(
     if use_hip(x):
         ext = hip_ext(required=True)
         Cout, _, k = weight.shape
-        mfma = (
-            x.dtype == torch.bfloat16 and groups == 1 and stride == 1
-        )
-        w = _conv_weight_mfma(weight) if mfma else weight.contiguous()
+        mfma = _conv_takes_mfma(x, k, stride, dilation, groups)
+        w = _conv_weight_mfma(weight) if mfma \
+            else weight.to(x.dtype).contiguous()
         return ext.conv1d_fused(
             x.contiguous(), w, _bias_f32(bias),
             Cout, k, stride, padding, dilation, groups,
@@ -255,7 +268,8 @@ def leaky_convtranspose1d(
         ext = hip_ext(required=True)
         Cin, Cout, k = weight.shape
         mfma = x.dtype == torch.bfloat16
-        w = _convt_weight_mfma(weight, stride) if mfma else weight.contiguous()
+        w = _convt_weight_mfma(weight, stride) if mfma \
+            else weight.to(x.dtype).contiguous()
         return ext.convtranspose1d_fused(
             x.contiguous(), w, _bias_f32(bias),
             Cout, k, stride, padding,

@@ -1,6 +1,8 @@
 """fp64 references and derived per-element error bounds for the
 channel-last HIP kernels (csrc/conv1d_cl.hip, csrc/resblock_cl.hip,
-csrc/elementwise.hip).
+csrc/elementwise.hip) and the channel-first conv family (csrc/conv1d.hip:
+``conv_ct_oracle``, ``convt_ct_oracle`` — same building blocks, same error
+model).
 
 Every reference runs in torch.float64 on CPU and mirrors the kernel's
 DOCUMENTED rounding points and nothing else:
@@ -128,16 +130,18 @@ def _cl(t: torch.Tensor) -> torch.Tensor:  # [B,T,C] <-> [B,C,T]
 
 
 def conv64(xa: torch.Tensor, w: torch.Tensor, padding: int, dilation: int,
-           dtype=D) -> torch.Tensor:
-    """Channel-last stride-1 conv, xa [B,T,Cin], w [Cout,Cin,k]."""
-    return _cl(F.conv1d(_cl(xa).to(dtype), w.to(dtype), None,
-                        padding=padding, dilation=dilation)).to(D)
+           dtype=D, stride: int = 1, groups: int = 1) -> torch.Tensor:
+    """Channel-last conv, xa [B,T,Cin], w [Cout,Cin/groups,k]."""
+    return _cl(F.conv1d(_cl(xa).to(dtype), w.to(dtype), None, stride=stride,
+                        padding=padding, dilation=dilation,
+                        groups=groups)).to(D)
 
 
-def abs_conv(xa, w, padding, dilation):
+def abs_conv(xa, w, padding, dilation, stride=1, groups=1):
     """A = sum |x'||w| — same routine on absolute values (f32, see
     module docstring)."""
-    return conv64(xa.abs(), w.abs(), padding, dilation, torch.float32)
+    return conv64(xa.abs(), w.abs(), padding, dilation, torch.float32,
+                  stride, groups)
 
 
 def row_mask(lens: Optional[torch.Tensor], B: int, T: int):
@@ -241,6 +245,105 @@ def convt_cl_oracle(x, w, bias, stride, padding, pre_slope=0.0,
     bound = elementwise_bound(ref, A, Cin * taps + 3, out_dtype,
                               masked=masked)
     return Oracle(ref, bound, masked)
+
+
+# --------------------------------------------------------------------------- #
+# channel-first conv family (csrc/conv1d.hip)
+# --------------------------------------------------------------------------- #
+def _pow2(v: float) -> bool:
+    m, _ = np.frexp(np.float32(v))
+    return float(m) == 0.5
+
+
+def _naive_operands(x, w, pre_slope):
+    """What the naive kernels multiply: x and w in x's dtype, the
+    pre-activation LeakyReLU in f32 WITHOUT the bf16 re-rounding of the MFMA
+    staging loop.  Returns (x', w', products_exact).  For bf16 and a
+    power-of-two slope (or none) x' is still bf16, hence ``pre_act`` and
+    exact products; otherwise every product rounds once in f32."""
+    if x.dtype == torch.bfloat16 and (pre_slope <= 0.0 or _pow2(pre_slope)):
+        return pre_act(x, pre_slope), w_bf16(w), True
+    v = x.detach().cpu().to(torch.float32)
+    if pre_slope > 0.0:
+        v = torch.where(v > 0, v, v * pre_slope)  # f32 arithmetic
+    return v.to(D), w.detach().cpu().to(x.dtype).to(D), False
+
+
+def conv_ct_oracle(x, w, bias, stride=1, padding=0, dilation=1, groups=1,
+                   pre_slope=0.0, act="none", post_slope=0.0, residual=None,
+                   path="mfma") -> Oracle:
+    """conv1d_fused on x [B,Cin,T], w [Cout,Cin/groups,k]; the output has
+    x's dtype.  act in {"none", "lrelu", "tanh"}.
+
+    path="mfma"   conv1d_mfma_kernel: bf16 operands, exact products,
+                  n = Cin·k + 3; the residual joins the f32 value before
+                  the single output rounding.
+    path="naive"  conv1d_naive_kernel: n = (Cin/groups)·k + 3 when the
+                  products are exact (see ``_naive_operands``), else
+                  2·(Cin/groups)·k + 3 as in ``depthwise_cl_oracle``.  The
+                  binding adds the residual with ``out.add_`` AFTER the
+                  kernel has stored: round to the output dtype, add, round
+                  again; the bound carries the first rounding, u_out·|y1|,
+                  next to the second.
+    """
+    Cout, cpg, k = w.shape
+    if path == "mfma":
+        assert x.dtype == torch.bfloat16 and stride == 1 and groups == 1
+        xa, wq, exact = pre_act(x, pre_slope), w_bf16(w), True
+    elif path == "naive":
+        xa, wq, exact = _naive_operands(x, w, pre_slope)
+    else:
+        raise ValueError(path)
+    n_terms = (1 if exact else 2) * cpg * k + 3
+    y = _cl(conv64(_cl(xa), wq, padding, dilation, D, stride, groups))
+    A = _cl(abs_conv(_cl(xa), wq, padding, dilation, stride, groups))
+    if bias is not None:
+        b = bias.detach().cpu().to(torch.float32).to(D).view(1, -1, 1)
+        y, A = y + b, A + b.abs()
+    if act == "lrelu":
+        y = lrelu64(y, post_slope)
+    elif act == "tanh":
+        y = torch.tanh(y)
+    elif act != "none":
+        raise ValueError(act)
+    carried = None
+    if residual is not None:
+        r = _f64(residual)
+        if path == "mfma":
+            y, A = y + r, A + r.abs()
+        else:
+            y1 = round_to(y, x.dtype)
+            carried = out_unit(x.dtype) * y1.abs()
+            y = y1 + r
+    ref = round_to(y, x.dtype)
+    bound = elementwise_bound(ref, A, n_terms, x.dtype, tanh=(act == "tanh"),
+                              carried=carried)
+    return Oracle(ref, bound, None)
+
+
+def convt_ct_oracle(x, w, bias, stride, padding, pre_slope=0.0,
+                    path="mfma") -> Oracle:
+    """convtranspose1d_fused on x [B,Cin,T], w [Cin,Cout,k];
+    n = Cin·ceil(k/stride) + 3 (doubled product count on the naive path when
+    the products round, as in ``conv_ct_oracle``)."""
+    Cin, Cout, k = w.shape
+    if path == "mfma":
+        assert x.dtype == torch.bfloat16
+        xa, wq, exact = pre_act(x, pre_slope), w_bf16(w), True
+    elif path == "naive":
+        xa, wq, exact = _naive_operands(x, w, pre_slope)
+    else:
+        raise ValueError(path)
+    y = F.conv_transpose1d(xa, wq, None, stride=stride, padding=padding)
+    A = F.conv_transpose1d(xa.abs().float(), wq.abs().float(), None,
+                           stride=stride, padding=padding).to(D)
+    if bias is not None:
+        b = bias.detach().cpu().to(torch.float32).to(D).view(1, -1, 1)
+        y, A = y + b, A + b.abs()
+    ref = round_to(y, x.dtype)
+    taps = -(-k // stride)  # taps that reach one output column
+    n_terms = (1 if exact else 2) * Cin * taps + 3
+    return Oracle(ref, elementwise_bound(ref, A, n_terms, x.dtype), None)
 
 
 # --------------------------------------------------------------------------- #
