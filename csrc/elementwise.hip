@@ -1253,3 +1253,188 @@ torch::Tensor ln_gelu_add(torch::Tensor y, torch::Tensor t, torch::Tensor mc,
 #undef LGA_LAUNCH
   return out;
 }
+
+// ------------------------------------------------------------------------- //
+// Per-row synthesis scales: one batch, a noise_scale / length_scale /
+// noise_w per request.  The scales stay f32 [B] on the device end to end: a
+// bf16 tensor of scales would round 0.8 to 0.80078 before the multiply, and
+// the scalar path multiplies by (float)0.8 in f32 and rounds the product
+// once.  Each kernel is bit-identical to its scalar counterpart run on that
+// row alone with the scalar scales[b].
+// ------------------------------------------------------------------------- //
+
+// the rounding an eager tensor of dtype T puts between two ops
+template <typename T> __device__ __forceinline__ float rnd_t(float v);
+template <> __device__ __forceinline__ float rnd_t<float>(float v) { return v; }
+template <> __device__ __forceinline__ float rnd_t<bf16>(float v) {
+  return rbf(v);
+}
+
+// prior_sample_kernel's body, ns read per batch row
+template <typename T>
+__global__ void prior_sample_rows_kernel(const T* __restrict__ m,
+                                         const T* __restrict__ logs,
+                                         const T* __restrict__ mask,  // [B,1,T]
+                                         const T* __restrict__ noise,
+                                         const float* __restrict__ ns_rows,
+                                         T* __restrict__ out, long C_T,
+                                         long T_len, long ms, long n) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  long b = i / C_T;
+  long t = i % T_len;
+  long j = b * ms + (i - b * C_T);
+  const float ns = ns_rows[b];
+  float msk = ld_f(mask + b * T_len + t);
+  float v = ld_f(m + j) + ld_f(noise + i) * __expf(ld_f(logs + j)) * ns;
+  st_f(out + i, v * msk);
+}
+
+torch::Tensor prior_sample_rows(torch::Tensor m, torch::Tensor logs,
+                                torch::Tensor mask, torch::Tensor noise,
+                                torch::Tensor noise_scale) {
+  TORCH_CHECK(m.is_cuda() && m.dim() == 3);
+  const long B = m.size(0), C = m.size(1), T = m.size(2);
+  auto dense_planes = [&](const torch::Tensor& t) {
+    return (T == 1 || t.stride(2) == 1) && (C == 1 || t.stride(1) == T);
+  };
+  TORCH_CHECK(m.sizes() == logs.sizes() && dense_planes(m) &&
+                  dense_planes(logs) &&
+                  (B == 1 || m.stride(0) == logs.stride(0)),
+              "prior_sample_rows: m/logs planes must be dense, one batch "
+              "stride");
+  TORCH_CHECK(logs.scalar_type() == m.scalar_type() &&
+                  mask.scalar_type() == m.scalar_type() &&
+                  noise.scalar_type() == m.scalar_type() && mask.is_cuda() &&
+                  noise.is_cuda(),
+              "prior_sample_rows: one dtype, one device");
+  TORCH_CHECK(noise.is_contiguous() && noise.numel() == B * C * T &&
+                  mask.is_contiguous() && mask.numel() == B * T,
+              "prior_sample_rows: noise [B,C,T], mask [B,1,T], contiguous");
+  const float* nsp = f32_vec(noise_scale, B, "prior_sample_rows: noise_scale");
+  const long ms = B > 1 ? m.stride(0) : C * T;
+  auto out = torch::empty({B, C, T}, m.options());
+  const long n = B * C * T;
+  if (!n) return out;
+  const int threads = 256;
+  DISPATCH_FT(m, "prior_sample_rows", {
+    hipLaunchKernelGGL(prior_sample_rows_kernel<scalar_t>,
+                       dim3((n + threads - 1) / threads), dim3(threads), 0,
+                       cur_stream(), (const scalar_t*)m.data_ptr(),
+                       (const scalar_t*)logs.data_ptr(),
+                       (const scalar_t*)mask.data_ptr(),
+                       (const scalar_t*)noise.data_ptr(), nsp,
+                       (scalar_t*)out.data_ptr(), C * T, T, ms, n);
+  });
+  return out;
+}
+
+// scale_mask_rows: z = noise * noise_w[b] * mask, the head of the duration
+// predictor's reverse pass.  Two eager multiplies: the product with the f32
+// scale is rounded to T once, the mask multiply (0/1, exact) once more; the
+// mask is multiplied, never selected, so signed zeros come out as ATen's.
+template <typename T>
+__global__ void scale_mask_rows_kernel(const T* __restrict__ noise,
+                                       const T* __restrict__ mask,  // [B,1,T]
+                                       const float* __restrict__ scales,
+                                       T* __restrict__ out, long C_T,
+                                       long T_len, long n) {
+#pragma clang fp contract(off)
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long b = i / C_T;
+  const long t = i % T_len;
+  const float v = rnd_t<T>(ld_f(noise + i) * scales[b]);
+  st_f(out + i, v * ld_f(mask + b * T_len + t));
+}
+
+torch::Tensor scale_mask_rows(torch::Tensor noise, torch::Tensor mask,
+                              torch::Tensor scales) {
+  TORCH_CHECK(noise.is_cuda() && noise.dim() == 3 && noise.is_contiguous(),
+              "scale_mask_rows: noise must be contiguous [B,C,T]");
+  const long B = noise.size(0), C = noise.size(1), T = noise.size(2);
+  TORCH_CHECK(mask.is_cuda() && mask.is_contiguous() &&
+                  mask.numel() == B * T &&
+                  mask.scalar_type() == noise.scalar_type(),
+              "scale_mask_rows: mask must be contiguous [B,1,T], noise's dtype");
+  const float* sp = f32_vec(scales, B, "scale_mask_rows: scales");
+  auto out = torch::empty_like(noise);
+  const long n = B * C * T;
+  if (!n) return out;
+  const int threads = 256;
+  DISPATCH_FT(noise, "scale_mask_rows", {
+    hipLaunchKernelGGL(scale_mask_rows_kernel<scalar_t>,
+                       dim3((n + threads - 1) / threads), dim3(threads), 0,
+                       cur_stream(), (const scalar_t*)noise.data_ptr(),
+                       (const scalar_t*)mask.data_ptr(), sp,
+                       (scalar_t*)out.data_ptr(), C * T, T, n);
+  });
+  return out;
+}
+
+// duration_rows: the eager chain
+//   w = exp(logw) * x_mask * length_scale;  w_ceil = ceil(w)
+//   y_lengths = clamp_min(sum(w_ceil, [1,2]), 1).long();  durs = int32(w_ceil)
+// in one launch, one wave per row.  Every tensor the chain materialises in
+// the activation dtype T is rounded to T here too: exp, both products, and
+// the row sum (ATen accumulates it in f32 and stores it as T).  w_ceil holds
+// integers, so the f32 accumulation is exact in any order below 2^24 frames.
+template <typename T>
+__global__ void duration_rows_kernel(const T* __restrict__ logw, long logw_bs,
+                                     const T* __restrict__ mask,  // [B,1,T]
+                                     const float* __restrict__ ls_rows,
+                                     int* __restrict__ durs,
+                                     long* __restrict__ y_lengths,
+                                     long T_len) {
+#pragma clang fp contract(off)
+  const long b = blockIdx.x;
+  const int lane = threadIdx.x;  // one wave per block
+  const float ls = ls_rows[b];
+  const T* lw = logw + b * logw_bs;
+  const T* mk = mask + b * T_len;
+  int* dr = durs + b * T_len;
+  float acc = 0.f;
+  for (long t = lane; t < T_len; t += WAVE) {
+    float w = rnd_t<T>(expf(ld_f(lw + t)));
+    w = rnd_t<T>(w * ld_f(mk + t));
+    w = rnd_t<T>(w * ls);
+    w = ceilf(w);
+    dr[t] = (int)w;
+    acc += w;
+  }
+#pragma unroll
+  for (int sh = 32; sh > 0; sh >>= 1) acc += __shfl_xor(acc, sh, WAVE);
+  if (lane == 0) {
+    float tot = rnd_t<T>(acc);
+    tot = tot < 1.f ? 1.f : tot;  // clamp_min: a NaN stays a NaN
+    y_lengths[b] = (long)tot;
+  }
+}
+
+std::vector<torch::Tensor> duration_rows(torch::Tensor logw,
+                                         torch::Tensor x_mask,
+                                         torch::Tensor length_scale) {
+  // logw [B,1,T] (unit time stride, any batch stride: the narrow of the
+  // duration flow's 2-channel state passes as is); x_mask [B,1,T] contiguous
+  TORCH_CHECK(logw.is_cuda() && logw.dim() == 3 && logw.size(1) == 1 &&
+                  (logw.size(2) == 1 || logw.stride(2) == 1),
+              "duration_rows: logw must be [B,1,T], unit time stride");
+  const long B = logw.size(0), T = logw.size(2);
+  TORCH_CHECK(x_mask.is_cuda() && x_mask.is_contiguous() &&
+                  x_mask.numel() == B * T &&
+                  x_mask.scalar_type() == logw.scalar_type(),
+              "duration_rows: x_mask must be contiguous [B,1,T], logw's dtype");
+  const float* lsp = f32_vec(length_scale, B, "duration_rows: length_scale");
+  auto durs = torch::empty({B, T}, logw.options().dtype(at::kInt));
+  auto y_lengths = torch::empty({B}, logw.options().dtype(at::kLong));
+  if (!B) return {durs, y_lengths};
+  const long bs = B > 1 ? logw.stride(0) : T;
+  DISPATCH_FT(logw, "duration_rows", {
+    hipLaunchKernelGGL(duration_rows_kernel<scalar_t>, dim3((unsigned)B),
+                       dim3(WAVE), 0, cur_stream(),
+                       (const scalar_t*)logw.data_ptr(), bs,
+                       (const scalar_t*)x_mask.data_ptr(), lsp,
+                       durs.data_ptr<int>(), y_lengths.data_ptr<long>(), T);
+  });
+  return {durs, y_lengths};
+}

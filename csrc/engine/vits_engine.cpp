@@ -90,6 +90,14 @@ torch::Tensor ln_gelu_add(torch::Tensor y, torch::Tensor t, torch::Tensor mc,
 std::vector<torch::Tensor> coupling_tail(torch::Tensor x0, torch::Tensor x1,
                                          torch::Tensor post, torch::Tensor mc,
                                          bool last);
+torch::Tensor prior_sample_rows(torch::Tensor m, torch::Tensor logs,
+                                torch::Tensor mask, torch::Tensor noise,
+                                torch::Tensor noise_scale);
+torch::Tensor scale_mask_rows(torch::Tensor noise, torch::Tensor mask,
+                              torch::Tensor scales);
+std::vector<torch::Tensor> duration_rows(torch::Tensor logw,
+                                         torch::Tensor x_mask,
+                                         torch::Tensor length_scale);
 
 namespace sonata {
 
@@ -941,8 +949,19 @@ torch::Tensor VitsEngine::dds_conv(torch::Tensor x, torch::Tensor mask,
 
 torch::Tensor VitsEngine::sdp_infer(torch::Tensor x, torch::Tensor mask,
                                     c10::optional<torch::Tensor> g,
-                                    double noise_w,
-                                    torch::Tensor noise) const {
+                                    double noise_w, torch::Tensor noise,
+                                    const torch::Tensor* noise_w_rows) const {
+  // z0 = noise * noise_w * mask.  Per row the scales are f32 [B]: the
+  // product is taken in f32 and rounded to the activation dtype once, as
+  // the scalar multiply does it
+  auto scaled_noise = [&]() -> torch::Tensor {
+    if (!noise_w_rows) return noise * noise_w * mask;
+    if (gpu())
+      return scale_mask_rows(noise.contiguous(), mask.contiguous(),
+                             *noise_w_rows);
+    return (noise.to(torch::kFloat) * noise_w_rows->view({-1, 1, 1}))
+               .to(noise.scalar_type()) * mask;
+  };
   if (gpu() && x.scalar_type() == torch::kBFloat16) {
     // channel-last SDP (mirrors vits.py _infer_cl): DDS/1x1 stages on
     // [B,T,C] rows, 2-channel flow state + spline stay channel-first
@@ -1012,7 +1031,7 @@ torch::Tensor VitsEngine::sdp_infer(torch::Tensor x, torch::Tensor mask,
     h = dds_cl(h, mc, c10::nullopt, "dp.convs");
     h = lin(h, "dp.proj") * mc;
 
-    auto z = noise * noise_w * mask;
+    auto z = scaled_noise();
     const long half = 1;
     auto conv_flow_cl = [&](torch::Tensor z, long idx) {
       std::string mod = "dp.flows." + std::to_string(idx);
@@ -1057,7 +1076,7 @@ torch::Tensor VitsEngine::sdp_infer(torch::Tensor x, torch::Tensor mask,
   x = dds_conv(x, mask, c10::nullopt, "dp.convs", 3, 3);
   x = conv(x, "dp.proj") * mask;
 
-  auto z = noise * noise_w * mask;
+  auto z = scaled_noise();
   // flows reversed: [EWA, CF0, Flip, CF1, Flip, CF2, Flip, CF3, Flip]
   // reversed -> [Flip, CF3, Flip, CF2, Flip, CF1, Flip, CF0, EWA];
   // python drops the final unused Flip pair: flows[:-2] + [flows[-1]]
@@ -1325,6 +1344,43 @@ VitsEngine::infer_encoder(torch::Tensor ids, torch::Tensor lengths,
                           c10::optional<torch::Tensor> sid,
                           double noise_scale, double length_scale,
                           double noise_w, const std::vector<int64_t>& seeds) {
+  return infer_encoder_impl(ids, lengths, sid, noise_scale, length_scale,
+                            noise_w, nullptr, seeds);
+}
+
+// per-row scales -> one f32 [B] device tensor each (f32 end to end: the
+// kernels multiply by scales[b] exactly as the scalar path by (float)scale)
+torch::Tensor VitsEngine::row_scales(const std::vector<double>& v, long B,
+                                     const char* what) const {
+  TORCH_CHECK((long)v.size() == B, what, ": expected ", B,
+              " per-row values, got ", v.size());
+  std::vector<float> f(v.begin(), v.end());
+  return torch::from_blob(f.data(), {B}, torch::kFloat).clone().to(device_);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+VitsEngine::infer_encoder(torch::Tensor ids, torch::Tensor lengths,
+                          c10::optional<torch::Tensor> sid,
+                          const std::vector<double>& noise_scale,
+                          const std::vector<double>& length_scale,
+                          const std::vector<double>& noise_w,
+                          const std::vector<int64_t>& seeds) {
+  const long B = ids.size(0);
+  RowScales rows{row_scales(noise_scale, B, "noise_scale"),
+                 row_scales(length_scale, B, "length_scale"),
+                 row_scales(noise_w, B, "noise_w")};
+  return infer_encoder_impl(ids, lengths, sid, 0.0, 0.0, 0.0, &rows, seeds);
+}
+
+// rows == nullptr: the scalar path, op for op what it always ran.  With
+// rows, only the three scale sites change (scale_mask_rows, duration_rows,
+// prior_sample_rows); equal rows take no shortcut.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>
+VitsEngine::infer_encoder_impl(torch::Tensor ids, torch::Tensor lengths,
+                               c10::optional<torch::Tensor> sid,
+                               double noise_scale, double length_scale,
+                               double noise_w, const RowScales* rows,
+                               const std::vector<int64_t>& seeds) {
   torch::NoGradGuard ng;
   ids = ids.to(device_);
   lengths = lengths.to(device_);
@@ -1352,24 +1408,42 @@ VitsEngine::infer_encoder(torch::Tensor ids, torch::Tensor lengths,
   torch::Tensor seeds_dev;
   torch::Tensor* seeds_once = fused_front() ? &seeds_dev : nullptr;
   auto sdp_noise = masked_noise(B, 2, ids.size(1), lengths, gens, seeds_once);
-  auto logw = sdp_infer(x, x_mask, g, noise_w, sdp_noise);
-  auto w = torch::exp(logw) * x_mask * length_scale;
-  auto w_ceil = torch::ceil(w);
-  auto y_lengths =
-      torch::clamp_min(torch::sum(w_ceil, {1, 2}), 1).to(torch::kLong);
+  auto logw = sdp_infer(x, x_mask, g, noise_w, sdp_noise,
+                        rows ? &rows->noise_w : nullptr);
+  // w_ceil (scalar and host per-row paths) or durs32 (duration_rows)
+  torch::Tensor w_ceil, durs32, y_lengths;
+  if (rows && gpu()) {
+    // one launch for the chain below, bit for bit (csrc/elementwise.hip)
+    auto dr = duration_rows(logw, x_mask.contiguous(), rows->length_scale);
+    durs32 = dr[0];
+    y_lengths = dr[1];
+  } else {
+    torch::Tensor w;
+    if (rows) {
+      auto wm = torch::exp(logw) * x_mask;
+      w = (wm.to(torch::kFloat) * rows->length_scale.view({-1, 1, 1}))
+              .to(wm.scalar_type());
+    } else {
+      w = torch::exp(logw) * x_mask * length_scale;
+    }
+    w_ceil = torch::ceil(w);
+    y_lengths =
+        torch::clamp_min(torch::sum(w_ceil, {1, 2}), 1).to(torch::kLong);
+  }
   long F_max = y_lengths.max().item<long>();
   auto y_mask = sequence_mask(y_lengths, F_max).to(x.dtype());
   torch::Tensor m_p_f, logs_p_f;
   if (stats.defined()) {
     // fused front end: one int32 durs, the F_max already on the host, and
     // one expand over the [B,2C,T] stats m_p and logs_p are the halves of
-    auto durs32 = w_ceil.squeeze(1).to(torch::kInt32);
+    if (!durs32.defined()) durs32 = w_ceil.squeeze(1).to(torch::kInt32);
     const long C = m_p.size(1);
     auto ef = expand(stats, durs32, y_lengths, F_max);
     m_p_f = ef.narrow(1, 0, C);
     logs_p_f = ef.narrow(1, C, C);
   } else {
-    auto durations = w_ceil.squeeze(1).to(torch::kLong);
+    auto durations = durs32.defined() ? durs32.to(torch::kLong)
+                                      : w_ceil.squeeze(1).to(torch::kLong);
     m_p_f = expand(m_p, durations, y_lengths);
     logs_p_f = expand(logs_p, durations, y_lengths);
   }
@@ -1383,8 +1457,15 @@ VitsEngine::infer_encoder(torch::Tensor ids, torch::Tensor lengths,
       m_p_f = m_p_f.contiguous();
       logs_p_f = logs_p_f.contiguous();
     }
-    z_p = prior_sample(m_p_f, logs_p_f, y_mask.contiguous(), pnoise,
-                       noise_scale);
+    z_p = rows ? prior_sample_rows(m_p_f, logs_p_f, y_mask.contiguous(),
+                                   pnoise, rows->noise_scale)
+               : prior_sample(m_p_f, logs_p_f, y_mask.contiguous(), pnoise,
+                              noise_scale);
+  } else if (rows) {
+    auto en = pnoise * torch::exp(logs_p_f);
+    auto sn = (en.to(torch::kFloat) * rows->noise_scale.view({-1, 1, 1}))
+                  .to(en.scalar_type());
+    z_p = (m_p_f + sn) * y_mask;
   } else {
     z_p = (m_p_f + pnoise * torch::exp(logs_p_f) * noise_scale) * y_mask;
   }
@@ -1403,6 +1484,20 @@ std::pair<torch::Tensor, torch::Tensor> VitsEngine::infer(
     torch::Tensor ids, torch::Tensor lengths,
     c10::optional<torch::Tensor> sid, double noise_scale,
     double length_scale, double noise_w, const std::vector<int64_t>& seeds) {
+  auto [z, y_mask, g] = infer_encoder(ids, lengths, sid, noise_scale,
+                                      length_scale, noise_w, seeds);
+  auto y_lengths = y_mask.squeeze(1).sum(-1).to(torch::kLong);
+  c10::optional<torch::Tensor> gopt;
+  if (g.defined()) gopt = g;
+  auto audio = decode(z, y_mask, gopt, y_lengths);
+  return {audio, y_lengths * cfg_.hop()};
+}
+
+std::pair<torch::Tensor, torch::Tensor> VitsEngine::infer(
+    torch::Tensor ids, torch::Tensor lengths,
+    c10::optional<torch::Tensor> sid, const std::vector<double>& noise_scale,
+    const std::vector<double>& length_scale,
+    const std::vector<double>& noise_w, const std::vector<int64_t>& seeds) {
   auto [z, y_mask, g] = infer_encoder(ids, lengths, sid, noise_scale,
                                       length_scale, noise_w, seeds);
   auto y_lengths = y_mask.squeeze(1).sum(-1).to(torch::kLong);

@@ -77,7 +77,35 @@ class VitsEngine {
                        c10::optional<torch::Tensor> g,
                        c10::optional<torch::Tensor> lengths);
 
+  // per-row synthesis scales: one noise_scale / length_scale / noise_w per
+  // batch row (length B), next to the per-row sid.  Row b renders as the
+  // scalar overloads render it alone with those three values; equal rows
+  // take no shortcut through the scalar path.
+  std::pair<torch::Tensor, torch::Tensor> infer(
+      torch::Tensor ids, torch::Tensor lengths,
+      c10::optional<torch::Tensor> sid,
+      const std::vector<double>& noise_scale,
+      const std::vector<double>& length_scale,
+      const std::vector<double>& noise_w, const std::vector<int64_t>& seeds);
+  std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> infer_encoder(
+      torch::Tensor ids, torch::Tensor lengths,
+      c10::optional<torch::Tensor> sid,
+      const std::vector<double>& noise_scale,
+      const std::vector<double>& length_scale,
+      const std::vector<double>& noise_w, const std::vector<int64_t>& seeds);
+
  private:
+  // f32 [B] on device_
+  struct RowScales {
+    torch::Tensor noise_scale, length_scale, noise_w;
+  };
+  torch::Tensor row_scales(const std::vector<double>& v, long B,
+                           const char* what) const;
+  std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> infer_encoder_impl(
+      torch::Tensor ids, torch::Tensor lengths,
+      c10::optional<torch::Tensor> sid, double noise_scale,
+      double length_scale, double noise_w, const RowScales* rows,
+      const std::vector<int64_t>& seeds);
   EngineConfig cfg_;
   torch::Device device_;
   torch::Dtype dtype_;
@@ -124,7 +152,8 @@ class VitsEngine {
                          long kernel) const;
   torch::Tensor sdp_infer(torch::Tensor x, torch::Tensor mask,
                           c10::optional<torch::Tensor> g, double noise_w,
-                          torch::Tensor noise) const;
+                          torch::Tensor noise,
+                          const torch::Tensor* noise_w_rows = nullptr) const;
   torch::Tensor generator(torch::Tensor z_masked,
                           c10::optional<torch::Tensor> g,
                           c10::optional<torch::Tensor> lengths) const;

@@ -41,6 +41,14 @@ torch::Tensor ln_gelu_add(torch::Tensor y, torch::Tensor t, torch::Tensor mc,
 torch::Tensor spline_tail(torch::Tensor inputs, torch::Tensor cumwidths,
                           torch::Tensor cumheights, torch::Tensor derivatives,
                           double tail_bound);
+torch::Tensor prior_sample_rows(torch::Tensor m, torch::Tensor logs,
+                                torch::Tensor mask, torch::Tensor noise,
+                                torch::Tensor noise_scale);
+torch::Tensor scale_mask_rows(torch::Tensor noise, torch::Tensor mask,
+                              torch::Tensor scales);
+std::vector<torch::Tensor> duration_rows(torch::Tensor logw,
+                                         torch::Tensor x_mask,
+                                         torch::Tensor length_scale);
 // conv1d.hip
 torch::Tensor conv1d_fused(torch::Tensor x, torch::Tensor w_perm,
                            c10::optional<torch::Tensor> bias, long Cout,
@@ -202,6 +210,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "and softplus'd derivatives",
         py::arg("inputs"), py::arg("cumwidths"), py::arg("cumheights"),
         py::arg("derivatives"), py::arg("tail_bound") = 5.0);
+  m.def("prior_sample_rows", &prior_sample_rows,
+        "prior_sample with noise_scale f32 [B] on the device, one per row",
+        py::arg("m"), py::arg("logs"), py::arg("mask"), py::arg("noise"),
+        py::arg("noise_scale"));
+  m.def("scale_mask_rows", &scale_mask_rows,
+        "z = noise * scales[b] * mask; scales f32 [B], product rounded once",
+        py::arg("noise"), py::arg("mask"), py::arg("scales"));
+  m.def("duration_rows", &duration_rows,
+        "exp(logw)*x_mask*length_scale[b] -> ceil -> (durs int32 [B,T], "
+        "y_lengths int64 [B]); bit-identical to the eager chain",
+        py::arg("logw"), py::arg("x_mask"), py::arg("length_scale"));
   m.def("conv1d_fused", &conv1d_fused, "MFMA conv1d with fused activations");
   m.def("convtranspose1d_fused", &convtranspose1d_fused,
         "MFMA transposed conv1d (phase-decomposed GEMMs)");
@@ -328,6 +347,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("sid") = py::none(), py::arg("noise_scale") = 0.667,
            py::arg("length_scale") = 1.0, py::arg("noise_w") = 0.8,
            py::arg("seeds") = std::vector<int64_t>{})
+      .def("infer_rows",
+           [](sonata::VitsEngine& e, torch::Tensor ids,
+              torch::Tensor lengths, c10::optional<torch::Tensor> sid,
+              std::vector<double> ns, std::vector<double> ls,
+              std::vector<double> nw, std::vector<int64_t> seeds) {
+             std::pair<torch::Tensor, torch::Tensor> r;
+             {
+               py::gil_scoped_release rel;
+               r = e.infer(ids, lengths, sid, ns, ls, nw, seeds);
+             }
+             return py::make_tuple(r.first, r.second);
+           },
+           py::arg("ids"), py::arg("lengths"), py::arg("sid"),
+           py::arg("noise_scale"), py::arg("length_scale"),
+           py::arg("noise_w"), py::arg("seeds") = std::vector<int64_t>{})
+      .def("infer_encoder_rows",
+           [](sonata::VitsEngine& e, torch::Tensor ids,
+              torch::Tensor lengths, c10::optional<torch::Tensor> sid,
+              std::vector<double> ns, std::vector<double> ls,
+              std::vector<double> nw, std::vector<int64_t> seeds) {
+             std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> r;
+             {
+               py::gil_scoped_release rel;
+               r = e.infer_encoder(ids, lengths, sid, ns, ls, nw, seeds);
+             }
+             return py::make_tuple(std::get<0>(r), std::get<1>(r),
+                                   std::get<2>(r));
+           },
+           py::arg("ids"), py::arg("lengths"), py::arg("sid"),
+           py::arg("noise_scale"), py::arg("length_scale"),
+           py::arg("noise_w"), py::arg("seeds") = std::vector<int64_t>{})
       .def("decode",
            [](sonata::VitsEngine& e, torch::Tensor z, torch::Tensor y_mask,
               c10::optional<torch::Tensor> g,

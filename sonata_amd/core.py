@@ -226,6 +226,15 @@ class SonataModel(abc.ABC):
         its rate, with AudioInfo(sample_rate=<its rate>)."""
         return False
 
+    @property
+    def supports_row_synthesis(self) -> bool:
+        """True when speak_batch / speak_batch_pcm / stream_open /
+        stream_synthesis_batch take synthesis= (one synthesis config or
+        None per row; stream_synthesis takes one): every row is rendered
+        with its own speaker and scales inside the one batch, and the
+        model's own config is left alone."""
+        return False
+
     # -- synthesis config (reference get/set_fallback..., typed not Any) ---- #
     @abc.abstractmethod
     def get_synthesis_config(self):

@@ -125,18 +125,31 @@ def _make_output_config(args, req: SynthesisRequest):
                              sample_rate=sample_rate, encoding=encoding)
 
 
-def _apply_synth_config(voice, args, req: SynthesisRequest) -> None:
+_SYNTH_KEYS = ("speaker_id", "length_scale", "noise_scale", "noise_w")
+
+
+def _apply_synth_config(voice, args) -> None:
+    """The command-line flags are the voice-wide default."""
     cfg = voice.get_synthesis_config()
-    sid = req.speaker_id if req.speaker_id is not None else args.speaker_id
-    if sid is not None:
-        cfg.speaker_id = sid
-    for name in ("length_scale", "noise_scale", "noise_w"):
-        v = getattr(req, name)
-        if v is None:
-            v = getattr(args, name)
+    for name in _SYNTH_KEYS:
+        v = getattr(args, name)
         if v is not None:
             setattr(cfg, name, v)
     voice.set_synthesis_config(cfg)
+
+
+def _request_synthesis(voice, req: SynthesisRequest):
+    """A JSON line's own speaker_id / scales as the SynthesisConfig of that
+    line alone: laid over the voice-wide default, which stays as it is.
+    None when the line sets none of them."""
+    if all(getattr(req, name) is None for name in _SYNTH_KEYS):
+        return None
+    cfg = voice.get_synthesis_config()
+    for name in _SYNTH_KEYS:
+        v = getattr(req, name)
+        if v is not None:
+            setattr(cfg, name, v)
+    return cfg
 
 
 def process_request(synth, args, req: SynthesisRequest, n: int,
@@ -147,7 +160,9 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
     from ..audio.wav import wav_bytes
     from ..core import Audio
 
-    _apply_synth_config(synth.model, args, req)
+    _apply_synth_config(synth.model, args)
+    synthesis = _request_synthesis(synth.model, req)
+    syn_kw = {"synthesis": synthesis} if synthesis is not None else {}
     out_cfg = _make_output_config(args, req)
     info = synth.audio_output_info()
     # WAV headers carry the result's own rate
@@ -159,7 +174,7 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
     total = 0
     if args.output_file:
         path = _enumerate_path(args.output_file, n)
-        audio = synth.synthesize_to_file(path, req.text, out_cfg)
+        audio = synth.synthesize_to_file(path, req.text, out_cfg, **syn_kw)
         total = len(audio.samples)
         log.info("wrote %s (%.1f ms audio, rtf %.4f)", path,
                  audio.duration_ms, audio.real_time_factor)
@@ -181,7 +196,8 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
             header_pos = stdout.tell() if stdout.seekable() else None
             stdout.write(header(0))
             for chunk in synth.synthesize_streamed(
-                    req.text, out_cfg, args.chunk_size, args.chunk_padding):
+                    req.text, out_cfg, args.chunk_size, args.chunk_padding,
+                    **syn_kw):
                 if enc != "pcm16":
                     stdout.write(g711.encode(
                         to_i16(chunk, peak_normalize=False), enc).tobytes())
@@ -199,9 +215,9 @@ def process_request(synth, args, req: SynthesisRequest, n: int,
             stdout.flush()
             return total
         else:
-            it = (synth.synthesize_lazy(req.text, out_cfg)
+            it = (synth.synthesize_lazy(req.text, out_cfg, **syn_kw)
                   if args.mode == "lazy"
-                  else synth.synthesize_parallel(req.text, out_cfg))
+                  else synth.synthesize_parallel(req.text, out_cfg, **syn_kw))
             parts = [a.samples for a in it]
             samples = (np.concatenate(parts) if parts
                        else np.zeros(0, dtype=np.float32))

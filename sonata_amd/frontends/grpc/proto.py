@@ -126,6 +126,9 @@ def _build_file() -> descriptor_pb2.FileDescriptorProto:
         (2, "text", "string", None),
         (3, "speech_args", "SpeechArgs", None),
         (4, "synthesis_mode", "enum:SynthesisMode", None),
+        # speaker and scales of this request alone; set fields override the
+        # voice's options, which stay as they are
+        (5, "synthesis_options", "SynthesisOptions", "optional"),
     ])
     message("VoiceSynthesisOptions", [
         (1, "voice_id", "string", None),

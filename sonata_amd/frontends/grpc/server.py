@@ -199,9 +199,10 @@ class SonataGrpcService:
     def GetSynthesisOptions(self, request, context):
         return self._options_msg(self._get(request.voice_id, context))
 
-    def SetSynthesisOptions(self, request, context):
-        v = self._get(request.voice_id, context)
-        opts = request.synthesis_options
+    @staticmethod
+    def _merged_options(v: _Voice, opts, context):
+        """The voice's SynthesisConfig with the set fields of `opts` laid
+        over it.  The speaker goes by name; an unknown one ends the RPC."""
         cfg = v.synth.get_synthesis_config()
         if opts.HasField("speaker"):
             speakers = v.synth.model.get_speakers() or {}
@@ -217,6 +218,26 @@ class SonataGrpcService:
             cfg.noise_scale = opts.noise_scale
         if opts.HasField("noise_w"):
             cfg.noise_w = opts.noise_w
+        return cfg
+
+    def _request_synthesis(self, v: _Voice, request, context):
+        """Utterance.synthesis_options as the SynthesisConfig of this
+        request alone (None when the field is absent): the voice's options
+        are read, never written."""
+        if not request.HasField("synthesis_options"):
+            return None
+        cfg = self._merged_options(v, request.synthesis_options, context)
+        check = getattr(v.synth.model, "check_synthesis_config", None)
+        if check is not None:
+            try:
+                check(cfg)
+            except ValueError as e:
+                context.abort(grpc.StatusCode.INVALID_ARGUMENT, str(e))
+        return cfg
+
+    def SetSynthesisOptions(self, request, context):
+        v = self._get(request.voice_id, context)
+        cfg = self._merged_options(v, request.synthesis_options, context)
         v.synth.set_synthesis_config(cfg)
         return self._options_msg(v)
 
@@ -225,9 +246,11 @@ class SonataGrpcService:
         out_cfg = self._speech_args_to_config(
             request.speech_args if request.HasField("speech_args") else None)
         rate = self._output_rate(v, out_cfg, context)
+        synthesis = self._request_synthesis(v, request, context)
         mode = request.synthesis_mode
         if mode == MODE_LAZY:
-            it = v.synth.synthesize_lazy(request.text, out_cfg, pcm=True)
+            it = v.synth.synthesize_lazy(request.text, out_cfg, pcm=True,
+                                         synthesis=synthesis)
             for audio in it:
                 yield MESSAGES["SynthesisResult"](
                     wav_samples=audio.as_wave_bytes(),
@@ -251,7 +274,8 @@ class SonataGrpcService:
         futures = [v.batcher.submit(sent, triple, pcm=pcm,
                                     silence_ms=silence_ms if pcm else None,
                                     sample_rate=rate if pcm else None,
-                                    encoding=enc if pcm else None)
+                                    encoding=enc if pcm else None,
+                                    synthesis=synthesis)
                    for sent in sentences]
         for f in futures:
             audio = f.result()
@@ -271,9 +295,11 @@ class SonataGrpcService:
 
         self._output_rate(v, out_cfg, context)
         enc = v.synth.output_encoding(out_cfg)
+        synthesis = self._request_synthesis(v, request, context)
         for chunk in v.synth.synthesize_streamed(
                 request.text, out_cfg,
-                REALTIME_CHUNK_SIZE, REALTIME_CHUNK_PADDING):
+                REALTIME_CHUNK_SIZE, REALTIME_CHUNK_PADDING,
+                synthesis=synthesis):
             if enc != "pcm16":
                 wav = g711.encode(to_i16(chunk), enc).tobytes()
             else:

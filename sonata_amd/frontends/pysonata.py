@@ -161,36 +161,43 @@ class Sonata:
         return Sonata(model)
 
     # --- synthesis ---------------------------------------------------- #
+    # `synthesis`: optional models.SynthesisConfig (speaker id and the three
+    # scales) of one call alone; the model's own options stay as they are.
     def synthesize(self, text: str,
-                   audio_output_config: Optional[AudioOutputConfig] = None
-                   ) -> Iterator[WaveSamples]:
-        return self.synthesize_parallel(text, audio_output_config)
+                   audio_output_config: Optional[AudioOutputConfig] = None,
+                   synthesis=None) -> Iterator[WaveSamples]:
+        return self.synthesize_parallel(text, audio_output_config,
+                                        synthesis=synthesis)
 
     def synthesize_lazy(self, text: str,
                         audio_output_config: Optional[AudioOutputConfig]
-                        = None) -> Iterator[WaveSamples]:
+                        = None, synthesis=None) -> Iterator[WaveSamples]:
         cfg = audio_output_config._to_internal() if audio_output_config else None
-        for a in self._synth.synthesize_lazy(text, cfg, pcm=True):
+        for a in self._synth.synthesize_lazy(text, cfg, pcm=True,
+                                             synthesis=synthesis):
             yield WaveSamples(a)
 
     def synthesize_parallel(self, text: str,
                             audio_output_config: Optional[AudioOutputConfig]
-                            = None) -> Iterator[WaveSamples]:
+                            = None, synthesis=None) -> Iterator[WaveSamples]:
         cfg = audio_output_config._to_internal() if audio_output_config else None
-        for a in self._synth.synthesize_parallel(text, cfg, pcm=True):
+        for a in self._synth.synthesize_parallel(text, cfg, pcm=True,
+                                                 synthesis=synthesis):
             yield WaveSamples(a)
 
     def synthesize_streamed(self, text: str,
                             audio_output_config: Optional[AudioOutputConfig]
                             = None, chunk_size: int = 45,
-                            chunk_padding: int = 3) -> Iterator[bytes]:
+                            chunk_padding: int = 3,
+                            synthesis=None) -> Iterator[bytes]:
         from ..audio import g711
         from ..audio.samples import to_i16, to_i16_bytes
 
         cfg = audio_output_config._to_internal() if audio_output_config else None
         enc = self._synth.output_encoding(cfg)
         for chunk in self._synth.synthesize_streamed(text, cfg, chunk_size,
-                                                     chunk_padding):
+                                                     chunk_padding,
+                                                     synthesis=synthesis):
             if enc != "pcm16":
                 yield g711.encode(to_i16(chunk), enc).tobytes()
             else:
@@ -198,9 +205,10 @@ class Sonata:
 
     def synthesize_to_file(self, filename: str, text: str,
                            audio_output_config: Optional[AudioOutputConfig]
-                           = None) -> None:
+                           = None, synthesis=None) -> None:
         cfg = audio_output_config._to_internal() if audio_output_config else None
-        self._synth.synthesize_to_file(filename, text, cfg)
+        self._synth.synthesize_to_file(filename, text, cfg,
+                                       synthesis=synthesis)
 
     # --- info --------------------------------------------------------- #
     @property

@@ -35,6 +35,9 @@ from ..ops import (
     leaky_convtranspose1d_cl,
     mask_tail_,
     prior_sample,
+    prior_sample_rows,
+    scale_mask_rows,
+    duration_rows,
 )
 from .config import VitsArchitecture
 
@@ -698,7 +701,10 @@ class StochasticDurationPredictor(nn.Module):
         if noise is None:
             noise = torch.randn((x.shape[0], 2, x.shape[2]),
                                 device=x.device, dtype=x.dtype)
-        z = noise * noise_scale * x_mask
+        if torch.is_tensor(noise_scale):  # f32 [B]: one scale per row
+            z = scale_mask_rows(noise, x_mask, noise_scale)
+        else:
+            z = noise * noise_scale * x_mask
         for flow in flows:
             z = flow(z, x_mask, g=x, reverse=True)
         z0, _ = z.chunk(2, dim=1)
@@ -721,7 +727,10 @@ class StochasticDurationPredictor(nn.Module):
         if noise is None:
             noise = torch.randn((x.shape[0], 2, x.shape[2]),
                                 device=x.device, dtype=x.dtype)
-        z = noise * noise_scale * x_mask
+        if torch.is_tensor(noise_scale):  # f32 [B]: one scale per row
+            z = scale_mask_rows(noise, x_mask, noise_scale)
+        else:
+            z = noise * noise_scale * x_mask
         flows = list(reversed(self.flows))
         flows = flows[:-2] + [flows[-1]]
         for flow in flows:
@@ -995,6 +1004,9 @@ class VitsModel(nn.Module):
     ) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
         """phoneme ids -> latent frames.  Returns (z, y_mask, g):
         z [B, C, F], y_mask [B, 1, F], g [B, gin, 1] or None.
+        Each of the three scales is a float (one value for the batch) or an
+        f32 [B] tensor (one per row; row b then renders as the float
+        scale[b] renders it alone).
         `generators`: one torch.Generator per utterance (deterministic,
         batch-composition-independent sampling)."""
         B = ids.shape[0]
@@ -1017,23 +1029,33 @@ class VitsModel(nn.Module):
         """Duration -> frames -> prior -> flow: the shape-DYNAMIC suffix
         of the encoder (frame count F is data-dependent; stays eager)."""
         B = m_p.shape[0]
-        w = torch.exp(logw) * x_mask * length_scale
-        w_ceil = torch.ceil(w)
-        y_lengths = torch.clamp_min(torch.sum(w_ceil, [1, 2]), 1).long()
+        if torch.is_tensor(length_scale):
+            # f32 [B], one per row: the chain below in one launch on the GPU
+            durations, y_lengths = duration_rows(logw, x_mask, length_scale)
+        else:
+            w = torch.exp(logw) * x_mask * length_scale
+            w_ceil = torch.ceil(w)
+            y_lengths = torch.clamp_min(
+                torch.sum(w_ceil, [1, 2]), 1).long()
+            durations = w_ceil.squeeze(1).long()
         # ONE host sync fetches all frame counts (the latency path was
         # paying several pipeline drains: sequence_mask .max().item(),
         # expand_states F_max, per-row noise .item()s)
         lens_list = y_lengths.tolist()
         F_max = max(lens_list)
         y_mask = sequence_mask(y_lengths, F_max).to(m_p.dtype)
-        durations = w_ceil.squeeze(1).long()
         m_p_f = expand_states(m_p, durations, y_lengths, F_max)
         logs_p_f = expand_states(logs_p, durations, y_lengths, F_max)
         prior_noise = masked_noise_rows(
             B, m_p_f.shape[1], m_p_f.shape[2], lens_list, generators,
             m_p.device, m_p.dtype,
         )
-        z_p = prior_sample(m_p_f, logs_p_f, y_mask, prior_noise, noise_scale)
+        if torch.is_tensor(noise_scale):
+            z_p = prior_sample_rows(m_p_f, logs_p_f, y_mask, prior_noise,
+                                    noise_scale)
+        else:
+            z_p = prior_sample(m_p_f, logs_p_f, y_mask, prior_noise,
+                               noise_scale)
         from ..ops import use_hip
 
         if use_hip(z_p):

@@ -13,6 +13,7 @@ converted via sonata_amd.models.onnx_import (weights-only importer).
 
 from __future__ import annotations
 
+import math
 import os
 import threading
 import time
@@ -147,6 +148,97 @@ class VitsVoice(SonataModel):
         s = sid if sid is not None else 0
         return torch.full((batch,), s, dtype=torch.long, device=self.device)
 
+    @property
+    def supports_row_synthesis(self) -> bool:
+        """speak_batch / speak_batch_pcm / stream_open / stream_synthesis*
+        take synthesis=: a SynthesisConfig (speaker and the three scales)
+        per row, all rows in one padded batch."""
+        return True
+
+    def check_synthesis_config(self, cfg: SynthesisConfig) -> None:
+        """Raise ValueError for a config no request may carry.  Run on the
+        host before any tensor is built: an out-of-range speaker would be
+        an out-of-range embedding index on the device."""
+        n = self.config.num_speakers
+        sid = cfg.speaker_id
+        if n > 1 and sid is not None:
+            if isinstance(sid, bool) or not isinstance(sid, (int, np.integer)):
+                raise ValueError(f"speaker_id {sid!r} is not an integer")
+            if not 0 <= int(sid) < n:
+                raise ValueError(
+                    f"speaker_id {sid} is outside [0, {n}) for this voice")
+        for name, lo_open in (("length_scale", True), ("noise_scale", False),
+                              ("noise_w", False)):
+            v = getattr(cfg, name)
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"{name} {v!r} is not a number") from None
+            if not math.isfinite(v):
+                raise ValueError(f"{name} must be finite, got {v}")
+            if v < 0 or (lo_open and v == 0):
+                raise ValueError(
+                    f"{name} must be {'> 0' if lo_open else '>= 0'}, got {v}")
+
+    def _resolve_synthesis(self, synthesis, B: int):
+        """(cfg, rows) for a batch of B.  rows is None when one config holds
+        for every row (synthesis=None, or rows that resolve to the same four
+        values): the batch then runs through the scalar entry with cfg,
+        exactly as without synthesis=.  Otherwise rows is one validated
+        SynthesisConfig per row, None entries filled with the voice's."""
+        base = self.get_synthesis_config()
+        if synthesis is None:
+            return base, None
+        if isinstance(synthesis, SynthesisConfig):
+            synthesis = [synthesis] * B
+        if len(synthesis) != B:
+            raise ValueError("one SynthesisConfig (or None) per row")
+        rows = []
+        for s in synthesis:
+            if s is None:
+                rows.append(base)
+                continue
+            self.check_synthesis_config(s)
+            rows.append(s.copy())
+        if not rows:
+            return base, None
+        key = lambda c: (c.speaker_id, float(c.noise_scale),  # noqa: E731
+                         float(c.length_scale), float(c.noise_w))
+        if all(key(r) == key(rows[0]) for r in rows[1:]):
+            return rows[0], None
+        return base, rows
+
+    def _encoder_rows(self, phonemes_batch, ids, lengths, rows, decode: bool):
+        """One batch with a speaker and three scales per row.  Row b's seed
+        is _utterance_seed(phonemes, rows[b].speaker_id): the audio a row
+        gets is the audio of that sentence alone with its config set
+        voice-wide.  decode=True runs the whole graph (audio, lengths);
+        False stops at the latent (z, y_mask, g)."""
+        B = len(rows)
+        sid_t = None
+        if self.config.num_speakers > 1:
+            sid_t = torch.tensor(
+                [int(r.speaker_id) if r.speaker_id is not None else 0
+                 for r in rows], dtype=torch.long, device=self.device)
+        ns = [float(r.noise_scale) for r in rows]
+        ls = [float(r.length_scale) for r in rows]
+        nw = [float(r.noise_w) for r in rows]
+        if self._engine is not None:
+            seeds = [_utterance_seed(p, r.speaker_id)
+                     for p, r in zip(phonemes_batch, rows)]
+            fn = (self._engine.infer_rows if decode
+                  else self._engine.infer_encoder_rows)
+            return fn(ids, lengths, sid_t, ns, ls, nw, seeds)
+        gens = []
+        for p, r in zip(phonemes_batch, rows):
+            gens.extend(self._generators([p], r.speaker_id))
+        f32 = dict(dtype=torch.float32, device=self.device)
+        fn = self.net.infer if decode else self.net.infer_encoder
+        return fn(ids, lengths, sid=sid_t,
+                  noise_scale=torch.tensor(ns, **f32),
+                  length_scale=torch.tensor(ls, **f32),
+                  noise_w=torch.tensor(nw, **f32), generators=gens)
+
     @torch.no_grad()
     def speak_one_sentence(self, phonemes: str) -> Audio:
         return self.speak_batch([phonemes])[0]
@@ -171,11 +263,11 @@ class VitsVoice(SonataModel):
         return y.unsqueeze(1), out_lengths
 
     @torch.no_grad()
-    def _infer_batch(self, phonemes_batch: Sequence[str]):
+    def _infer_batch(self, phonemes_batch: Sequence[str], synthesis=None):
         """Id-encode and run one padded batch.  Returns the decoder output
         [B, 1, T] and per-row lengths, both on the model's device, and the
         wall time of the inference in ms."""
-        cfg = self.get_synthesis_config()
+        cfg, rows = self._resolve_synthesis(synthesis, len(phonemes_batch))
         id_lists = [self._encode_ids(p) for p in phonemes_batch]
         B = len(id_lists)
         T = max((len(i) for i in id_lists), default=1)
@@ -186,6 +278,15 @@ class VitsVoice(SonataModel):
             lengths[b] = len(il)
         ids = ids.to(self.device)
         lengths = lengths.to(self.device)
+        if rows is not None:
+            t0 = time.perf_counter()
+            with self._infer_lock, stage_timer("infer", self.device):
+                audio, audio_lengths = self._encoder_rows(
+                    phonemes_batch, ids, lengths, rows, decode=True)
+                if self.device.type == "cuda":
+                    torch.cuda.synchronize(self.device)
+            infer_ms = (time.perf_counter() - t0) * 1000.0
+            return audio, audio_lengths, infer_ms
         gens = self._generators(phonemes_batch, cfg.speaker_id)
 
         t0 = time.perf_counter()
@@ -262,7 +363,8 @@ class VitsVoice(SonataModel):
 
     @torch.no_grad()
     def speak_batch(self, phonemes_batch: Sequence[str],
-                    prosody=None, sample_rate=None) -> List[Audio]:
+                    prosody=None, sample_rate=None,
+                    synthesis=None) -> List[Audio]:
         """True padded [B, T] batching (the reference loops batch=1:
         piper/src/lib.rs:425-437 — batching is a headline improvement).
 
@@ -270,8 +372,13 @@ class VitsVoice(SonataModel):
         None; applied on the device tensor before the single host copy.
         `sample_rate`: optional output rate, one int or one int-or-None per
         row; each distinct rate is converted on the device after prosody
-        (ops.resample_rows) and copied on its own."""
-        audio, audio_lengths, infer_ms = self._infer_batch(phonemes_batch)
+        (ops.resample_rows) and copied on its own.
+        `synthesis`: optional per-row sequence of SynthesisConfig or None
+        (None: the voice's config when the call runs).  Rows with different
+        speakers or scales share the one batch; each row is rendered as it
+        would be alone with its config set voice-wide."""
+        audio, audio_lengths, infer_ms = self._infer_batch(
+            phonemes_batch, synthesis)
         B = len(phonemes_batch)
         info = self.audio_output_info()
         out: List[Audio] = []
@@ -352,7 +459,7 @@ class VitsVoice(SonataModel):
     @torch.no_grad()
     def speak_batch_pcm(self, phonemes_batch: Sequence[str], prosody=None,
                         silence_ms=None, sample_rate=None,
-                        encoding=None) -> List[PcmAudio]:
+                        encoding=None, synthesis=None) -> List[PcmAudio]:
         """speak_batch whose results are wire-format int16: what
         `Audio.as_wave_bytes` gives for speak_batch's samples with
         `silence_ms` of silence merged on (per row or one value; rounded to
@@ -367,7 +474,8 @@ class VitsVoice(SonataModel):
         On cuda the 8-bit rows of a rate are one ops.g711_rows launch with
         per-row laws and one host copy of a quarter of the float bytes; a
         batch that is all one kind costs the launches and copies of the
-        int16 path."""
+        int16 path.
+        `synthesis` is speak_batch's: one SynthesisConfig or None per row."""
         B = len(phonemes_batch)
         if silence_ms is None or isinstance(silence_ms, (int, float)):
             silence_ms = [silence_ms] * B
@@ -384,11 +492,14 @@ class VitsVoice(SonataModel):
                 kw["prosody"] = prosody
             if converts:
                 kw["sample_rate"] = rates
+            if synthesis is not None:
+                kw["synthesis"] = synthesis
             audios = self.speak_batch(phonemes_batch, **kw)
             return [PcmAudio.from_audio(a, s, e)
                     for a, s, e in zip(audios, sil, encs)]
 
-        audio, audio_lengths, infer_ms = self._infer_batch(phonemes_batch)
+        audio, audio_lengths, infer_ms = self._infer_batch(
+            phonemes_batch, synthesis)
         if prosody is not None:
             audio, audio_lengths = self._prosody_rows(
                 audio, audio_lengths, prosody)
@@ -419,14 +530,22 @@ class VitsVoice(SonataModel):
 
     @torch.no_grad()
     def stream_synthesis(
-        self, phonemes: str, chunk_size: int = 45, chunk_padding: int = 3
+        self, phonemes: str, chunk_size: int = 45, chunk_padding: int = 3,
+        synthesis: Optional[SynthesisConfig] = None,
     ) -> Iterator[np.ndarray]:
         """Yield waveform chunks: encoder runs once, the HiFi-GAN decoder
         runs per adaptive chunk with overlap-discard + crossfade seams
-        (reference SpeechStreamer, piper/src/lib.rs:765-858)."""
+        (reference SpeechStreamer, piper/src/lib.rs:765-858).
+        `synthesis`: this stream's speaker and scales (None: the voice's).
+        The graph-replayed phase 1 bakes none of them in: noise_w scales the
+        noise before the replay, the other two act in the eager phase 2."""
         from ..utils.graphs import phase1_enabled
 
-        cfg = self.get_synthesis_config()
+        if synthesis is not None:
+            self.check_synthesis_config(synthesis)
+            cfg = synthesis.copy()
+        else:
+            cfg = self.get_synthesis_config()
         ids_l = self._encode_ids(phonemes)
         ids = torch.tensor([ids_l], dtype=torch.long, device=self.device)
         lengths = torch.tensor([len(ids_l)], dtype=torch.long, device=self.device)
@@ -632,7 +751,7 @@ class VitsVoice(SonataModel):
     @torch.no_grad()
     def stream_open(self, phonemes_batch: Sequence[str], chunk_size=45,
                     chunk_padding: int = 3, prosody=None,
-                    sample_rate=None) -> List["StreamState"]:
+                    sample_rate=None, synthesis=None) -> List["StreamState"]:
         """Encode a list of sentences in ONE batched encoder call and return
         one StreamState per sentence, to be advanced by stream_round.
         `chunk_size` is an int or one int per sentence.  Speaker and scales
@@ -649,7 +768,10 @@ class VitsVoice(SonataModel):
         its chunks, what ops.resample_rows gives on its whole audio (after
         prosody): the filter's carry stays on the device between rounds
         (ops.resample_poly_stream_rows), and a round may emit an empty
-        chunk."""
+        chunk.
+        `synthesis`: one SynthesisConfig or None per sentence, as in
+        speak_batch: streams of different speakers and scales share the one
+        encoder call."""
         B = len(phonemes_batch)
         native = self.config.sample_rate
         rates = [None if r == native else r
@@ -661,9 +783,9 @@ class VitsVoice(SonataModel):
             chunk_size = [chunk_size] * B
         chunk_size = [int(c) for c in chunk_size]
         assert len(chunk_size) == B, "one chunk_size per sentence"
+        cfg, rows = self._resolve_synthesis(synthesis, B)
         if B == 0:
             return []
-        cfg = self.get_synthesis_config()
         id_lists = [self._encode_ids(p) for p in phonemes_batch]
         T = max(len(i) for i in id_lists)
         ids = torch.zeros((B, T), dtype=torch.long)
@@ -676,7 +798,12 @@ class VitsVoice(SonataModel):
         sid = self._sid_tensor(B, cfg.speaker_id)
         with self._infer_lock:
             with stage_timer("encode", self.device):
-                if self._engine is not None:
+                if rows is not None:
+                    z, y_mask, g = self._encoder_rows(
+                        phonemes_batch, ids, lengths, rows, decode=False)
+                    if g is not None and (not g.numel()):
+                        g = None
+                elif self._engine is not None:
                     z, y_mask, g = self._engine.infer_encoder(
                         ids, lengths, sid, cfg.noise_scale, cfg.length_scale,
                         cfg.noise_w,
@@ -935,7 +1062,8 @@ class VitsVoice(SonataModel):
     def stream_synthesis_batch(self, phonemes_batch: Sequence[str],
                                chunk_size=45, chunk_padding: int = 3,
                                pcm: bool = False, prosody=None,
-                               sample_rate=None, encoding=None):
+                               sample_rate=None, encoding=None,
+                               synthesis=None):
         """stream_synthesis for a list of sentences at once: yields (index,
         chunk) with, per index, the chunk boundaries, total length and seams
         of stream_synthesis.  One encoder call, then one decode per round
@@ -949,10 +1077,13 @@ class VitsVoice(SonataModel):
         `sample_rate` is stream_open's too: an index's chunks then
         concatenate to ops.resample_rows of its stream without a rate, and
         a chunk may be empty.
-        `encoding` is stream_round's, one value or one per sentence."""
+        `encoding` is stream_round's, one value or one per sentence.
+        `synthesis` is stream_open's, one SynthesisConfig or None per
+        sentence."""
         self._round_laws(phonemes_batch, encoding)  # checked before opening
         states = self.stream_open(phonemes_batch, chunk_size, chunk_padding,
-                                  prosody=prosody, sample_rate=sample_rate)
+                                  prosody=prosody, sample_rate=sample_rate,
+                                  synthesis=synthesis)
         pins = _PinnedPair() if self.device.type == "cuda" else None
         try:
             with self._infer_lock:

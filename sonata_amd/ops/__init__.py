@@ -59,6 +59,9 @@ from .functional import (  # noqa: F401,E402
     layer_norm_ct,
     fused_gate,
     prior_sample,
+    prior_sample_rows,
+    scale_mask_rows,
+    duration_rows,
     expand_states,
     leaky_conv1d,
     leaky_convtranspose1d,

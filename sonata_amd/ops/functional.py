@@ -90,6 +90,71 @@ def prior_sample(
 
 
 # --------------------------------------------------------------------------- #
+# Per-row synthesis scales: one noise_scale / noise_w / length_scale per batch
+# row.  The scales are f32 [B] end to end: each product is taken in f32 and
+# rounded to the activation dtype once, as a multiply by the Python float is
+# (a bf16 tensor of scales would round 0.8 to 0.80078 first).
+# --------------------------------------------------------------------------- #
+def _rows_f32(scales: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    return scales.to(device=like.device, dtype=torch.float32).contiguous()
+
+
+def _mul_rows(x: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """x [B,...] times scales[b]: f32 product, one rounding to x's dtype."""
+    s = scales.view(-1, *([1] * (x.dim() - 1)))
+    return (x.float() * s).to(x.dtype)
+
+
+def prior_sample_rows(
+    m: torch.Tensor,
+    logs: torch.Tensor,
+    mask: torch.Tensor,
+    noise: torch.Tensor,
+    noise_scale: torch.Tensor,
+) -> torch.Tensor:
+    """prior_sample with noise_scale f32 [B]: row b is prior_sample of that
+    row alone with float(noise_scale[b]).  m / logs may be the two halves of
+    one [B,2C,T] tensor (dense planes, free batch stride)."""
+    ns = _rows_f32(noise_scale, m)
+    if use_hip(m):
+        ext = hip_ext(required=True)
+        return ext.prior_sample_rows(m, logs, mask.contiguous(),
+                                     noise.contiguous(), ns)
+    return (m + _mul_rows(noise * torch.exp(logs), ns)) * mask
+
+
+def scale_mask_rows(
+    noise: torch.Tensor, mask: torch.Tensor, scales: torch.Tensor
+) -> torch.Tensor:
+    """noise [B,C,T] * scales[b] * mask [B,1,T]: bit-equal, row by row, to
+    `noise * float(scales[b]) * mask`."""
+    s = _rows_f32(scales, noise)
+    if use_hip(noise):
+        ext = hip_ext(required=True)
+        return ext.scale_mask_rows(noise.contiguous(), mask.contiguous(), s)
+    return _mul_rows(noise, s) * mask
+
+
+def duration_rows(
+    logw: torch.Tensor, x_mask: torch.Tensor, length_scale: torch.Tensor
+):
+    """ceil(exp(logw) * x_mask * length_scale[b]) -> (durs int32 [B,T],
+    y_lengths int64 [B], at least 1): the eager duration chain with a scale
+    per row, every rounding of the activation dtype kept (the row sum's
+    too).  One launch on the GPU."""
+    ls = _rows_f32(length_scale, logw)
+    if use_hip(logw):
+        ext = hip_ext(required=True)
+        if logw.shape[2] != 1 and logw.stride(2) != 1:
+            logw = logw.contiguous()
+        durs, y_lengths = ext.duration_rows(logw, x_mask.contiguous(), ls)
+        return durs, y_lengths
+    w_ceil = torch.ceil(_mul_rows(torch.exp(logw) * x_mask, ls))
+    y_lengths = torch.clamp_min(torch.sum(w_ceil, [1, 2]), 1).long()
+    return w_ceil.squeeze(1).to(torch.int32), y_lengths
+
+
+# --------------------------------------------------------------------------- #
 # Length regulator: expand phoneme states to frame states by durations
 # --------------------------------------------------------------------------- #
 def expand_states(

@@ -24,6 +24,52 @@ from ..audio.samples import silence_samples
 from ..core import Audio, AudioInfo, PcmAudio, SonataModel
 
 
+def _check_synthesis(model, synthesis):
+    """A request's own SynthesisConfig, validated by the model at submit
+    time (ValueError) and copied; None stays None: the model's config at
+    the time the batch runs."""
+    if synthesis is None:
+        return None
+    check = getattr(model, "check_synthesis_config", None)
+    if check is not None:
+        check(synthesis)
+    return synthesis.copy()
+
+
+def _synthesis_key(cfg):
+    if cfg is None:
+        return None
+    return (cfg.speaker_id, float(cfg.noise_scale), float(cfg.length_scale),
+            float(cfg.noise_w))
+
+
+def _by_synthesis(items, cfg_of):
+    """items grouped by config, first-seen order: [(cfg or None, [items])]"""
+    groups = {}
+    for it in items:
+        cfg = cfg_of(it)
+        groups.setdefault(_synthesis_key(cfg), (cfg, []))[1].append(it)
+    return list(groups.values())
+
+
+class _config_set:
+    """Set the model's voice-wide config around one call: the route for a
+    model without supports_row_synthesis."""
+
+    def __init__(self, model, cfg):
+        self.model, self.cfg = model, cfg
+
+    def __enter__(self):
+        if self.cfg is not None:
+            self.saved = self.model.get_synthesis_config()
+            self.model.set_synthesis_config(self.cfg)
+
+    def __exit__(self, *exc):
+        if self.cfg is not None:
+            self.model.set_synthesis_config(self.saved)
+        return False
+
+
 class DynamicBatcher:
     def __init__(self, model: SonataModel, max_batch: int = 64,
                  max_wait_ms: float = 3.0):
@@ -32,7 +78,7 @@ class DynamicBatcher:
         self.max_wait = max_wait_ms / 1000.0
         # items: (phonemes, future, prosody triple or None, pcm,
         #         silence_ms or None, output sample rate or None,
-        #         wire encoding)
+        #         wire encoding, SynthesisConfig or None)
         self._q: "queue.Queue[Optional[tuple]]" = queue.Queue()
         self._worker = threading.Thread(target=self._run, daemon=True,
                                         name="sonata_batcher")
@@ -44,7 +90,8 @@ class DynamicBatcher:
                pcm: bool = False,
                silence_ms: Optional[float] = None,
                sample_rate: Optional[int] = None,
-               encoding: Optional[str] = None) -> "Future[Audio]":
+               encoding: Optional[str] = None,
+               synthesis=None) -> "Future[Audio]":
         """Queue one sentence; the future resolves with its Audio.
         `prosody`: optional (speed, volume, pitch) applied to this request's
         row by the model (speak_batch(prosody=...)); rows of one batch may
@@ -60,9 +107,17 @@ class DynamicBatcher:
         `encoding`: optional wire encoding of a pcm request ("pcm16",
         "ulaw", "alaw"); it rides with the request too, and requests with
         different encodings still share one speak_batch_pcm.  Anything else
-        raises ValueError here."""
+        raises ValueError here.
+        `synthesis`: optional SynthesisConfig (speaker and scales) of this
+        request alone; it rides with the request as the prosody triple does,
+        and requests with different speakers or scales still share one
+        speak_batch* call (speak_batch(synthesis=...)).  None: the model's
+        config when the batch runs.  A speaker or scale the model refuses
+        raises ValueError here.  A model without supports_row_synthesis gets
+        the bucket group by group, each with its config set around it."""
         if self._closed:
             raise RuntimeError("batcher closed")
+        synthesis = _check_synthesis(self.model, synthesis)
         assert pcm or not silence_ms, "silence_ms rides with pcm requests"
         encoding = check_encoding(encoding)
         assert pcm or encoding == "pcm16", "encoding rides with pcm requests"
@@ -76,7 +131,7 @@ class DynamicBatcher:
         f: "Future[Audio]" = Future()
         self._q.put((phonemes, f, tuple(prosody) if prosody is not None
                      else None, bool(pcm), silence_ms, sample_rate,
-                     encoding))
+                     encoding, synthesis))
         return f
 
     def synthesize(self, phonemes: str) -> Audio:
@@ -123,10 +178,27 @@ class DynamicBatcher:
                 start = i
 
     def _run_bucket(self, bucket: List[tuple]) -> None:
+        synth = [it[7] for it in bucket]
+        if all(c is None for c in synth):
+            return self._run_rows(bucket)
+        if getattr(self.model, "supports_row_synthesis", False):
+            return self._run_rows(bucket, synth)
+        for cfg, group in _by_synthesis(bucket, lambda it: it[7]):
+            try:
+                with _config_set(self.model, cfg):
+                    self._run_rows(group)
+            except BaseException as e:  # noqa: BLE001 - propagate to callers
+                for it in group:
+                    if not it[1].done():
+                        it[1].set_exception(e)
+
+    def _run_rows(self, bucket: List[tuple], synthesis=None) -> None:
         phonemes = [it[0] for it in bucket]
         prosody = [it[2] for it in bucket]
         kw = {"prosody": prosody} if any(
             p is not None for p in prosody) else {}
+        if synthesis is not None:
+            kw["synthesis"] = synthesis
         rates = [it[5] for it in bucket]
         host_rate = False
         if any(r is not None for r in rates):
@@ -177,11 +249,14 @@ class _StreamHandle:
     once opened, its model state."""
 
     __slots__ = ("phonemes", "chunk_size", "chunk_padding", "pcm", "q",
-                 "cancelled", "state", "prosody", "sample_rate", "encoding")
+                 "cancelled", "state", "prosody", "sample_rate", "encoding",
+                 "synthesis")
 
     def __init__(self, phonemes, chunk_size, chunk_padding, pcm,
-                 prosody=None, sample_rate=None, encoding="pcm16"):
+                 prosody=None, sample_rate=None, encoding="pcm16",
+                 synthesis=None):
         self.phonemes = phonemes
+        self.synthesis = synthesis
         self.encoding = encoding
         self.prosody = tuple(prosody) if prosody is not None else None
         self.sample_rate = sample_rate
@@ -266,7 +341,7 @@ class StreamBatcher:
     def open(self, phonemes: str, chunk_size: int = 45,
              chunk_padding: int = 3, pcm: bool = False, prosody=None,
              sample_rate: Optional[int] = None,
-             encoding: Optional[str] = None):
+             encoding: Optional[str] = None, synthesis=None):
         """Start one stream; returns the iterator of its chunks (float32
         arrays, or int16 with pcm=True), those model.stream_synthesis
         yields for the same arguments.
@@ -284,9 +359,16 @@ class StreamBatcher:
         `encoding`: "ulaw" or "alaw" makes the chunks uint8 G.711 codes
         (model.stream_round(encoding=...): the codes of the int16 chunks
         pcm=True gives); mu-law and A-law streams share a round.  None or
-        "pcm16" changes nothing; anything else raises ValueError here."""
+        "pcm16" changes nothing; anything else raises ValueError here.
+        `synthesis`: optional SynthesisConfig of this stream alone; streams
+        with different speakers or scales still share one model.stream_open
+        (stream_open(synthesis=...)).  None: the model's config when the
+        stream is opened.  What the model refuses raises ValueError here.  A
+        model without supports_row_synthesis opens the newcomers group by
+        group, each with its config set around the call."""
         if self._closed:
             raise RuntimeError("stream batcher closed")
+        synthesis = _check_synthesis(self.model, synthesis)
         encoding = check_encoding(encoding)
         if sample_rate is not None:
             native = self.model.audio_output_info().sample_rate
@@ -296,7 +378,7 @@ class StreamBatcher:
                 check_rate(native, sample_rate)
                 sample_rate = int(sample_rate)
         h = _StreamHandle(phonemes, chunk_size, chunk_padding, pcm, prosody,
-                          sample_rate, encoding)
+                          sample_rate, encoding, synthesis)
         self._q.put(h)
         return _StreamIter(h)
 
@@ -345,22 +427,31 @@ class StreamBatcher:
         new = [h for h in new if not h.cancelled]
         opened: List[_StreamHandle] = []
         # one stream_open per chunk_padding (in practice: one)
+        rows = getattr(self.model, "supports_row_synthesis", False)
         for pad in sorted({h.chunk_padding for h in new}):
-            group = [h for h in new if h.chunk_padding == pad]
-            try:
-                kw = {"prosody": [h.prosody for h in group]} if any(
-                    h.prosody is not None for h in group) else {}
-                if any(h.sample_rate is not None for h in group):
-                    kw["sample_rate"] = [h.sample_rate for h in group]
-                states = self.model.stream_open(
-                    [h.phonemes for h in group],
-                    [h.chunk_size for h in group], pad, **kw)
-            except BaseException as e:  # noqa: BLE001 - reaches the callers
-                self._fail(group, e)
-                continue
-            for h, s in zip(group, states):
-                h.state = s
-            opened.extend(group)
+            padded = [h for h in new if h.chunk_padding == pad]
+            if rows or all(h.synthesis is None for h in padded):
+                groups = [(None, padded)]
+            else:
+                groups = _by_synthesis(padded, lambda h: h.synthesis)
+            for cfg, group in groups:
+                try:
+                    kw = {"prosody": [h.prosody for h in group]} if any(
+                        h.prosody is not None for h in group) else {}
+                    if any(h.sample_rate is not None for h in group):
+                        kw["sample_rate"] = [h.sample_rate for h in group]
+                    if rows and any(h.synthesis is not None for h in group):
+                        kw["synthesis"] = [h.synthesis for h in group]
+                    with _config_set(self.model, cfg):
+                        states = self.model.stream_open(
+                            [h.phonemes for h in group],
+                            [h.chunk_size for h in group], pad, **kw)
+                except BaseException as e:  # noqa: BLE001 - reaches callers
+                    self._fail(group, e)
+                    continue
+                for h, s in zip(group, states):
+                    h.state = s
+                opened.extend(group)
         return opened
 
     @staticmethod

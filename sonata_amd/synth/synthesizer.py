@@ -32,6 +32,7 @@ from ..audio.samples import (generate_silence, merge, silence_samples,
                              to_i16)
 from ..audio.wav import write_wav_file, write_wav_file_g711
 from ..core import Audio, AudioInfo, PcmAudio, SonataModel
+from .batcher import _config_set, _StreamIter
 
 # percent(0-100) -> parameter ranges (reference synth/src/lib.rs:13-15)
 RATE_RANGE = (0.5, 5.5)
@@ -192,17 +193,34 @@ class SonataSpeechSynthesizer:
                 and getattr(dev, "type", None) == "cuda"
                 and (cfg.is_noop or self.device_prosody(cfg)))
 
+    def _model_batch(self, name: str, sentences: List[str], synthesis,
+                     **kw):
+        """model.speak_batch / speak_batch_pcm for one request.  Its
+        SynthesisConfig (speaker and scales; None: the model's own) goes in
+        as the rows' synthesis=; a model without supports_row_synthesis has
+        it set voice-wide around the call."""
+        fn = getattr(self.model, name)
+        if synthesis is None:
+            return fn(sentences, **kw)
+        if getattr(self.model, "supports_row_synthesis", False):
+            return fn(sentences, synthesis=[synthesis] * len(sentences),
+                      **kw)
+        with _config_set(self.model, synthesis):
+            return fn(sentences, **kw)
+
     def _speak_device_prosody(self, sentences: List[str],
-                              cfg: AudioOutputConfig) -> List[Audio]:
+                              cfg: AudioOutputConfig,
+                              synthesis=None) -> List[Audio]:
         """One speak_batch with cfg's prosody applied on the device; _post
         then only appends silence."""
         triple = cfg.prosody_triple()
-        batch = self.model.speak_batch(
-            sentences, prosody=[triple] * len(sentences))
+        batch = self._model_batch(
+            "speak_batch", sentences, synthesis,
+            prosody=[triple] * len(sentences))
         return [self._post(a, cfg, prosody_done=True) for a in batch]
 
     def _speak_rate(self, sentences: List[str], cfg: AudioOutputConfig,
-                    rate: int) -> List[Audio]:
+                    rate: int, synthesis=None) -> List[Audio]:
         """One batch at another output rate.  On the device: prosody and the
         conversion inside speak_batch, silence here.  Else the float batch
         is finished on the host: prosody, resample_poly, silence."""
@@ -210,14 +228,16 @@ class SonataSpeechSynthesizer:
             kw = {}
             if not cfg.is_noop:
                 kw["prosody"] = [cfg.prosody_triple()] * len(sentences)
-            batch = self.model.speak_batch(sentences, sample_rate=rate, **kw)
+            batch = self._model_batch("speak_batch", sentences, synthesis,
+                                      sample_rate=rate, **kw)
             return [self._post(a, cfg, prosody_done=True) for a in batch]
         if self.device_prosody(cfg):
-            batch = self.model.speak_batch(
-                sentences, prosody=[cfg.prosody_triple()] * len(sentences))
+            batch = self._model_batch(
+                "speak_batch", sentences, synthesis,
+                prosody=[cfg.prosody_triple()] * len(sentences))
             return [self._post(a, cfg, prosody_done=True, rate=rate)
                     for a in batch]
-        batch = self.model.speak_batch(sentences)
+        batch = self._model_batch("speak_batch", sentences, synthesis)
         return [self._post(a, cfg, rate=rate) for a in batch]
 
     @staticmethod
@@ -248,7 +268,8 @@ class SonataSpeechSynthesizer:
         return Audio(samples, audio.info, audio.inference_ms)
 
     def _speak_pcm(self, sentences: List[str],
-                   cfg: Optional[AudioOutputConfig]) -> List[PcmAudio]:
+                   cfg: Optional[AudioOutputConfig],
+                   synthesis=None) -> List[PcmAudio]:
         """One batch as wire-format PcmAudio, bytes equal to
         as_wave_bytes() of the float path.  A model with speak_batch_pcm
         gets prosody (when the device path is on), appended silence and the
@@ -263,12 +284,12 @@ class SonataSpeechSynthesizer:
             # the conversion runs on the host, so the float path is kept up
             # to it (device prosody first, where it is on)
             if self.device_prosody(cfg):
-                batch = self.model.speak_batch(
-                    sentences,
+                batch = self._model_batch(
+                    "speak_batch", sentences, synthesis,
                     prosody=[cfg.prosody_triple()] * len(sentences))
                 return [self.to_pcm(a, cfg, prosody_done=True, rate=rate)
                         for a in batch]
-            batch = self.model.speak_batch(sentences)
+            batch = self._model_batch("speak_batch", sentences, synthesis)
             return [self.to_pcm(a, cfg, rate=rate) for a in batch]
         if getattr(self.model, "supports_device_pcm", False) \
                 and not host_prosody:
@@ -277,14 +298,15 @@ class SonataSpeechSynthesizer:
             kw = {"sample_rate": rate} if rate is not None else {}
             if enc != "pcm16":
                 kw["encoding"] = enc
-            return self.model.speak_batch_pcm(
-                sentences,
+            return self._model_batch(
+                "speak_batch_pcm", sentences, synthesis,
                 prosody=[triple] * len(sentences) if triple else None,
                 silence_ms=cfg.appended_silence_ms if cfg else None, **kw)
         if rate is not None:
             return [PcmAudio.from_audio(a, encoding=enc)
-                    for a in self._speak_rate(sentences, cfg, rate)]
-        batch = self.model.speak_batch(sentences)
+                    for a in self._speak_rate(sentences, cfg, rate,
+                                              synthesis)]
+        batch = self._model_batch("speak_batch", sentences, synthesis)
         return [self.to_pcm(a, cfg) for a in batch]
 
     def to_pcm(self, audio: Audio, cfg: Optional[AudioOutputConfig],
@@ -306,48 +328,59 @@ class SonataSpeechSynthesizer:
     # ------------------------------------------------------------------ #
     def synthesize_lazy(
         self, text: str, output_config: Optional[AudioOutputConfig] = None,
-        pcm: bool = False,
+        pcm: bool = False, synthesis=None,
     ) -> Iterator[Audio]:
         """Pull-based: each sentence synthesized when consumed
         (reference SonataSpeechStreamLazy, synth/src/lib.rs:282-307).
         `pcm=True` yields PcmAudio (int16, converted on the device when the
-        model can) instead of float Audio; the wire bytes are the same."""
+        model can) instead of float Audio; the wire bytes are the same.
+        `synthesis`: optional SynthesisConfig (speaker and scales) of this
+        request alone; the model's own config is neither read nor changed."""
         rate = self.output_rate(output_config)
         self.output_encoding(output_config)
         phonemes = self.model.phonemize_text(text)
         for sent in phonemes:
             if pcm:
-                yield self._speak_pcm([sent], output_config)[0]
+                yield self._speak_pcm([sent], output_config, synthesis)[0]
                 continue
             if rate is not None:
-                yield self._speak_rate([sent], output_config, rate)[0]
+                yield self._speak_rate([sent], output_config, rate,
+                                       synthesis)[0]
                 continue
             if self.device_prosody(output_config):
-                yield self._speak_device_prosody([sent], output_config)[0]
+                yield self._speak_device_prosody([sent], output_config,
+                                                 synthesis)[0]
+                continue
+            if synthesis is not None:
+                yield self._post(self._model_batch(
+                    "speak_batch", [sent], synthesis)[0], output_config)
                 continue
             yield self._post(self.model.speak_one_sentence(sent), output_config)
 
     def synthesize_parallel(
         self, text: str, output_config: Optional[AudioOutputConfig] = None,
-        pcm: bool = False,
+        pcm: bool = False, synthesis=None,
     ) -> Iterator[Audio]:
         """Eager batched synthesis of all sentences.  The reference fans
         out per-sentence rayon tasks (synth/src/lib.rs:316-320); here the
         model's true padded batch path does the fan-out on-device.
-        `pcm=True` yields PcmAudio, as in synthesize_lazy."""
+        `pcm=True` yields PcmAudio, as in synthesize_lazy; `synthesis` is
+        synthesize_lazy's too."""
         self.output_encoding(output_config)
         phonemes = self.model.phonemize_text(text)
         if len(phonemes) == 0:
             return iter(())
         if pcm:
-            return iter(self._speak_pcm(list(phonemes), output_config))
+            return iter(self._speak_pcm(list(phonemes), output_config,
+                                        synthesis))
         rate = self.output_rate(output_config)
         if rate is not None:
-            return iter(self._speak_rate(list(phonemes), output_config, rate))
+            return iter(self._speak_rate(list(phonemes), output_config, rate,
+                                         synthesis))
         if self.device_prosody(output_config):
             return iter(self._speak_device_prosody(list(phonemes),
-                                                   output_config))
-        batch = self.model.speak_batch(list(phonemes))
+                                                   output_config, synthesis))
+        batch = self._model_batch("speak_batch", list(phonemes), synthesis)
         return iter([self._post(a, output_config) for a in batch])
 
     def synthesize_streamed(
@@ -356,6 +389,7 @@ class SonataSpeechSynthesizer:
         output_config: Optional[AudioOutputConfig] = None,
         chunk_size: int = 45,
         chunk_padding: int = 3,
+        synthesis=None,
     ) -> Iterator[np.ndarray]:
         """Realtime mode: producer thread pushes waveform chunks through a
         queue while the caller consumes (reference RealtimeSpeechStream,
@@ -373,8 +407,23 @@ class SonataSpeechSynthesizer:
         the rate rides into the model's stream path instead, after prosody
         there: no StreamResampler is built and empty chunks are dropped.
         It applies when no prosody is left to run here, on the host, which
-        would have to come before the conversion."""
+        would have to come before the conversion.
+        `synthesis` is synthesize_lazy's: it rides into whichever stream
+        path serves the request (the stream batcher, the model's batched
+        streams or its single stream)."""
         rate = self.output_rate(output_config)
+        check = getattr(self.model, "check_synthesis_config", None)
+        if synthesis is not None and check is not None:
+            check(synthesis)
+        rows = getattr(self.model, "supports_row_synthesis", False)
+        # one request's config for a model call: as synthesis= where the
+        # model takes it, else set voice-wide while the stream runs
+        syn_one = ({"synthesis": synthesis}
+                   if synthesis is not None and rows else {})
+        syn_rows = ({"synthesis": [synthesis]}
+                    if synthesis is not None and rows else {})
+        syn_open = {"synthesis": synthesis} if synthesis is not None else {}
+        held = None if rows else synthesis
         phonemes = self.model.phonemize_text(text)
         info = self.model.audio_output_info()
         q: "queue.Queue" = queue.Queue()
@@ -414,22 +463,29 @@ class SonataSpeechSynthesizer:
                         if self.stream_batcher is not None:
                             it = self.stream_batcher.open(
                                 sent, cs, chunk_padding, prosody=triple,
-                                **kw)
+                                **kw, **syn_open)
                         else:
                             it = (c for _, c in
                                   self.model.stream_synthesis_batch(
                                       [sent], cs, chunk_padding,
                                       prosody=(None if triple is None
-                                               else [triple]), **kw))
+                                               else [triple]), **kw,
+                                      **syn_rows))
                     elif (self.stream_batcher is not None
                             and self.model.supports_streaming_output):
-                        it = self.stream_batcher.open(sent, cs, chunk_padding)
+                        it = self.stream_batcher.open(sent, cs, chunk_padding,
+                                                      **syn_open)
                     elif self.model.supports_streaming_output:
                         it = self.model.stream_synthesis(
-                            sent, cs, chunk_padding
+                            sent, cs, chunk_padding, **syn_one
                         )
                     else:
-                        it = iter([self.model.speak_one_sentence(sent).samples])
+                        it = iter([self._model_batch(
+                            "speak_batch", [sent], synthesis)[0].samples])
+                    # (the stream batcher sets the config itself for a model
+                    # that takes none per stream)
+                    if held is not None and not isinstance(it, _StreamIter):
+                        it = self._held(it, held)
                     rs = (StreamResampler(info.sample_rate, rate)
                           if rate is not None and not model_rate else None)
                     for chunk in it:
@@ -465,11 +521,19 @@ class SonataSpeechSynthesizer:
                 raise q.get()
             yield item
 
+    def _held(self, it, synthesis):
+        """Run a model stream with `synthesis` set voice-wide while it
+        lasts: a model without supports_row_synthesis reads its config when
+        the stream starts."""
+        with _config_set(self.model, synthesis):
+            yield from it
+
     def synthesize_to_file(
         self,
         path: str,
         text: str,
         output_config: Optional[AudioOutputConfig] = None,
+        synthesis=None,
     ) -> Audio:
         """Collect parallel synthesis into one WAV (reference
         synthesize_to_file, synth/src/lib.rs:170-198).  With a G.711
@@ -479,7 +543,8 @@ class SonataSpeechSynthesizer:
         pieces: List[np.ndarray] = []
         info = self.model.audio_output_info()
         inference_ms = 0.0
-        for audio in self.synthesize_parallel(text, output_config):
+        for audio in self.synthesize_parallel(text, output_config,
+                                              synthesis=synthesis):
             info = audio.info  # the result's own rate
             pieces.append(audio.samples)
             inference_ms += audio.inference_ms
