@@ -89,6 +89,13 @@ __global__ __launch_bounds__(512) void conv1d_cl_kernel(
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  // this thread's NT bias columns, loaded once ahead of the GEMM
+  float br[NT];
+#pragma unroll
+  for (int nj = 0; nj < NT; ++nj) {
+    const int co = n0 + wc * WN + nj * 16 + il;
+    br[nj] = (bias && co < Cout) ? bias[co] : 0.f;
+  }
 
   const bf16* xb = x + (long)b * Tin * Cin;
   const long row0 = t0 - pad;  // x row staged at Xs[0]
@@ -184,6 +191,22 @@ __global__ __launch_bounds__(512) void conv1d_cl_kernel(
   const bf16* rb = resid ? resid + (long)b * Tout * Cout : nullptr;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
+    // the 4 x NT residuals of this row tile, issued together and
+    // branch-free: an element that is masked or outside the tensor reads
+    // the tile's first (live, in-bounds) element and drops it
+    bf16 rv[4][NT];
+    if (rb) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const long t = t0 + wr * WM + mi * 16 + kl * 4 + rg;
+#pragma unroll
+        for (int nj = 0; nj < NT; ++nj) {
+          const int co = n0 + wc * WN + nj * 16 + il;
+          rv[rg][nj] =
+              rb[(t < lim && co < Cout) ? t * Cout + co : t0 * Cout + n0];
+        }
+      }
+    }
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
       const long t = t0 + wr * WM + mi * 16 + kl * 4 + rg;
@@ -196,10 +219,10 @@ __global__ __launch_bounds__(512) void conv1d_cl_kernel(
         float v = 0.f;
         if (live) {
           v = acc[mi][nj][rg];
-          if (bias) v += bias[co];
+          if (bias) v += br[nj];
           if (act_mode == ACT_LRELU) v = lrelu_(v, post_slope);
           else if (act_mode == ACT_TANH) v = tanhf(v);
-          if (rb) v += bf2f(rb[t * Cout + co]);
+          if (rb) v += bf2f(rv[rg][nj]);
         }
         ob[t * Cout + co] = f2bf(v);
       }
@@ -265,6 +288,13 @@ __global__ __launch_bounds__(512) void conv1d_cl_wdirect_kernel(
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  // this thread's NT bias columns, loaded once ahead of the GEMM
+  float br[NT];
+#pragma unroll
+  for (int nj = 0; nj < NT; ++nj) {
+    const int co = n0 + wc * WN + nj * 16 + il;
+    br[nj] = (bias && co < Cout) ? bias[co] : 0.f;
+  }
 
   const bf16* xb = x + (long)b * Tin * Cin;
   const long row0 = t0 - pad;
@@ -346,6 +376,22 @@ __global__ __launch_bounds__(512) void conv1d_cl_wdirect_kernel(
   const bf16* rb = resid ? resid + (long)b * Tout * Cout : nullptr;
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi) {
+    // the 4 x NT residuals of this row tile, issued together and
+    // branch-free: an element that is masked or outside the tensor reads
+    // the tile's first (live, in-bounds) element and drops it
+    bf16 rv[4][NT];
+    if (rb) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const long t = t0 + wr * WM + mi * 16 + kl * 4 + rg;
+#pragma unroll
+        for (int nj = 0; nj < NT; ++nj) {
+          const int co = n0 + wc * WN + nj * 16 + il;
+          rv[rg][nj] =
+              rb[(t < lim && co < Cout) ? t * Cout + co : t0 * Cout + n0];
+        }
+      }
+    }
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg) {
       const long t = t0 + wr * WM + mi * 16 + kl * 4 + rg;
@@ -358,10 +404,10 @@ __global__ __launch_bounds__(512) void conv1d_cl_wdirect_kernel(
         float v = 0.f;
         if (live) {
           v = acc[mi][nj][rg];
-          if (bias) v += bias[co];
+          if (bias) v += br[nj];
           if (act_mode == ACT_LRELU) v = lrelu_(v, post_slope);
           else if (act_mode == ACT_TANH) v = tanhf(v);
-          if (rb) v += bf2f(rb[t * Cout + co]);
+          if (rb) v += bf2f(rv[rg][nj]);
         }
         ob[t * Cout + co] = f2bf(v);
       }
@@ -431,6 +477,13 @@ __global__ __launch_bounds__(512) void convt1d_cl_kernel(
     for (int i = 0; i < MT; ++i)
 #pragma unroll
       for (int j = 0; j < NT; ++j) acc[r][i][j] = {0.f, 0.f, 0.f, 0.f};
+  // this thread's NT bias columns, loaded once ahead of the GEMM
+  float br[NT];
+#pragma unroll
+  for (int nj = 0; nj < NT; ++nj) {
+    const int co = n0 + wc * WN + nj * 16 + il;
+    br[nj] = (bias && co < Cout) ? bias[co] : 0.f;
+  }
 
   const bf16* xb = x + (long)b * Tin * Cin;
   const long row0 = v0 - (KR - 1);  // tap m reads x[v - m]
@@ -543,7 +596,7 @@ __global__ __launch_bounds__(512) void convt1d_cl_kernel(
           float out_v = 0.f;
           if (live) {
             out_v = acc[r][mi][nj][rg];
-            if (bias) out_v += bias[co];
+            if (bias) out_v += br[nj];
           }
           ob[t * Cout + co] = f2bf(out_v);
         }
@@ -779,6 +832,13 @@ __global__ __launch_bounds__(512) void conv1d_direct_cl_kernel(
   for (int i = 0; i < MT; ++i)
 #pragma unroll
     for (int j = 0; j < NT; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+  // this thread's NT bias columns, loaded once ahead of the GEMM
+  float br[NT];
+#pragma unroll
+  for (int nj = 0; nj < NT; ++nj) {
+    const int co = n0 + wc * WN + nj * 16 + il;
+    br[nj] = (bias && co < Cout) ? bias[co] : 0.f;
+  }
 
   const bf16* xb = x + (long)b * Tin * Cin;
   // per-lane row bases (constant across the K loop)
@@ -814,6 +874,8 @@ __global__ __launch_bounds__(512) void conv1d_direct_cl_kernel(
     }
   }
 
+  // (residuals stay per element here: batching them costs this
+  // register-bound, undispatched variant a block per CU)
   bf16* ob = out + (long)b * Tout * Cout;
   const bf16* rb = resid ? resid + (long)b * Tout * Cout : nullptr;
 #pragma unroll
@@ -830,7 +892,7 @@ __global__ __launch_bounds__(512) void conv1d_direct_cl_kernel(
         float v = 0.f;
         if (live) {
           v = acc[mi][nj][rg];
-          if (bias) v += bias[co];
+          if (bias) v += br[nj];
           if (act_mode == ACT_LRELU) v = lrelu_(v, post_slope);
           else if (act_mode == ACT_TANH) v = tanhf(v);
           if (rb) v += bf2f(rb[t * Cout + co]);

@@ -14,14 +14,48 @@
 // recomputed per block).  GEMM orientation identical to conv1d_cl.hip:
 // A = time rows (k-contiguous channel-last), B = [co][ci] weight taps,
 // K = Cin in 32-deep LDS slices.
+//
+// LDS layout: ONE buffer, carved in this order (sizes as before the carve):
+//   Xs [XR][BKP]      bf16  staged x rows of one K slice (pre-activated)
+//   Xt [XTR][XTP]     bf16  conv1's output tile, XTP = BN + 8
+//   Ws [TC][BN][BKP]  bf16  weight taps of one staging window
+// GEMM 2 reads Xt rows up to XTR-1+(k-1) for output rows >= BM that the
+// epilogue discards; with Ws behind Xt those reads stay inside the buffer
+// (static_assert below).  After GEMM 2's last barrier all three are dead,
+// and the staged epilogue 2 (STAGED) reuses the buffer from offset 0 as
+// eight wave-private f32 tiles St[WM][CW+4] (CW = min(WN, 64) columns at a
+// time): the wave writes acc + b2 there in the MFMA layout and reads it
+// back row-wise, one lane per 8 consecutive channels, so the residual, the
+// accum and the output move 16 bytes per lane.
 #include "common.h"
 
 #define BK 32
 #define BKP 40
 #define XTROWS 128
 
-template <int BN, int WGN, int TC, int XR, int XTR>
-__global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
+// Orders a wave's LDS writes before its own lanes' reads of what OTHER
+// lanes wrote (and the reverse for reuse).  A wave's LDS operations execute
+// in order; this only stops the compiler from moving them across.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Waves per SIMD that the block's LDS footprint allows on a 160 KiB CU
+// (8 waves per block, 2 per SIMD).  Handed to __launch_bounds__ so that
+// the register allocation never costs a block that LDS leaves room for.
+constexpr int rb_pair_lds_bytes(int BN, int TC, int XR, int XTR) {
+  return (XR * BKP + XTR * (BN + 8) + TC * BN * BKP) * 2;
+}
+constexpr int rb_pair_waves(int BN, int TC, int XR, int XTR) {
+  const int blocks = 160 * 1024 / rb_pair_lds_bytes(BN, TC, XR, XTR);
+  return blocks >= 4 ? 8 : 2 * blocks;
+}
+
+template <int BN, int WGN, int TC, int XR, int XTR, bool STAGED>
+__global__ __launch_bounds__(512, rb_pair_waves(BN, TC, XR, XTR))
+void resblock_pair_cl_kernel(
     const bf16* __restrict__ x,    // [B][T][C]
     const bf16* __restrict__ w1,   // [k][CP][CP] (dilated conv) or sliced
     const float* __restrict__ b1,  // [C]
@@ -72,9 +106,24 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
     return;
   }
 
-  __shared__ bf16 Xs[XROWS_MAX][BKP];
-  __shared__ bf16 Xt[XTR][XTP];
-  __shared__ bf16 Ws[TC][BN][BKP];
+  // one buffer, carved Xs | Xt | Ws (see the header comment)
+  constexpr int XS_BYTES = XROWS_MAX * BKP * 2;
+  constexpr int XT_BYTES = XTR * XTP * 2;
+  constexpr int WS_BYTES = TC * BN * BKP * 2;
+  // staged epilogue 2: wave-private f32 tiles of CW columns, pitch CW + 4
+  constexpr int CW = WN < 64 ? WN : 64;
+  constexpr int SP = CW + 4;
+  static_assert(XS_BYTES % 16 == 0 && XT_BYTES % 16 == 0, "carve alignment");
+  static_assert(10 * XTP * 2 <= WS_BYTES,
+                "GEMM 2's discarded Xt rows (k <= 11) must stay inside Ws");
+  static_assert(8 * WM * SP * 4 <= XS_BYTES + XT_BYTES + WS_BYTES,
+                "staged epilogue tiles must fit the existing footprint");
+  __shared__ __attribute__((aligned(16))) unsigned char
+      smem[XS_BYTES + XT_BYTES + WS_BYTES];
+  bf16 (*Xs)[BKP] = reinterpret_cast<bf16 (*)[BKP]>(smem);
+  bf16 (*Xt)[XTP] = reinterpret_cast<bf16 (*)[XTP]>(smem + XS_BYTES);
+  bf16 (*Ws)[BN][BKP] =
+      reinterpret_cast<bf16 (*)[BN][BKP]>(smem + XS_BYTES + XT_BYTES);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -83,6 +132,15 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
   const int wc = wid % WGN;
   const int kl = lane >> 4;
   const int il = lane & 15;
+
+  // this thread's NT bias columns, loaded once ahead of its GEMM (b2r is
+  // loaded ahead of GEMM 2: live across GEMM 1 it costs C=64 a block/CU)
+  float b1r[NT], b2r[NT];
+#pragma unroll
+  for (int nj = 0; nj < NT; ++nj) {
+    const int co = wc * WN + nj * 16 + il;
+    b1r[nj] = co < C ? b1[co] : 0.f;
+  }
 
   const bf16* xb = x + (long)b * T * C;
   const int pad1 = (k - 1) * dil / 2;
@@ -185,7 +243,7 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
         const int co = wc * WN + nj * 16 + il;
         float v = 0.f;
         if (live && co < C)
-          v = lrelu_(acc[mi][nj][rg] + b1[co], 0.1f);
+          v = lrelu_(acc[mi][nj][rg] + b1r[nj], 0.1f);
         Xt[m][co] = f2bf(v);
       }
     }
@@ -193,6 +251,11 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
   __syncthreads();
 
   // ================= GEMM2: out = conv2(xt) + x =======================
+#pragma unroll
+  for (int nj = 0; nj < NT; ++nj) {
+    const int co = wc * WN + nj * 16 + il;
+    b2r[nj] = co < C ? b2[co] : 0.f;
+  }
 #pragma unroll
   for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -236,25 +299,96 @@ __global__ __launch_bounds__(512) void resblock_pair_cl_kernel(
   // epilogue2: bias2 + residual x (+ xs accumulation) + scale + mask
   bf16* ob = out + (long)b * T * C;
   const bf16* ab = accum ? accum + (long)b * T * C : nullptr;
+  if constexpr (STAGED) {
+    // Through LDS, 16 bytes per lane.  The host dispatches this only for
+    // C % 8 == 0 and 16-byte aligned x / accum / out, so a lane's 8
+    // channels are all inside C or all outside, and its rows are aligned.
+    // Same f32 operations in the same order as the element path below.
+    constexpr int NH = WN / CW;     // column passes over the wave's tile
+    constexpr int NTH = CW / 16;    // MFMA column tiles per pass
+    constexpr int LPR = CW / 8;     // lanes per row, 8 channels each
+    constexpr int RPP = 64 / LPR;   // rows per 64-lane read
+    constexpr int G = WM / RPP;     // 16-byte groups per lane and pass
+    float* St = reinterpret_cast<float*>(smem) + wid * (WM * SP);
+    const int er = lane / LPR;
+    const int ec = (lane % LPR) * 8;
+    // the last barrier of GEMM 2 is behind every wave: Xs, Xt, Ws are dead
 #pragma unroll
-  for (int mi = 0; mi < MT; ++mi) {
+    for (int h = 0; h < NH; ++h) {
+      if (h > 0) wave_lds_sync();  // pass h-1 fully read before overwriting
 #pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      const int m2 = wr * WM + mi * 16 + kl * 4 + rg;
-      const long t = t0 + m2;
-      if (m2 >= BM || t >= T) continue;
-      const bool live = t < lim;
+      for (int mi = 0; mi < MT; ++mi)
 #pragma unroll
-      for (int nj = 0; nj < NT; ++nj) {
-        const int co = wc * WN + nj * 16 + il;
-        if (co >= C) continue;
-        float v = 0.f;
-        if (live) {
-          v = acc[mi][nj][rg] + b2[co] + bf2f(xb[t * C + co]);
-          if (ab) v += bf2f(ab[t * C + co]);
-          v *= out_scale;
+        for (int rg = 0; rg < 4; ++rg)
+#pragma unroll
+          for (int nj = 0; nj < NTH; ++nj)
+            St[(mi * 16 + kl * 4 + rg) * SP + nj * 16 + il] =
+                acc[mi][h * NTH + nj][rg] + b2r[h * NTH + nj];
+      wave_lds_sync();
+      const int col0 = wc * WN + h * CW + ec;
+      const bool col_ok = col0 < C;
+      auto finish = [&](auto has_ab) {
+        long off[G];
+        bool st_ok[G], live[G];
+        ulonglong2 xv[G], av[G];
+        // every global load of the pass first, branch-free: a group that
+        // stores nothing or a masked row reads the tile's first (live,
+        // in-bounds) row and drops it
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const int m2 = wr * WM + g * RPP + er;
+          const long t = t0 + m2;
+          st_ok[g] = col_ok && m2 < BM && t < T;
+          live[g] = t < lim;
+          off[g] = t * C + col0;
+          const long ld = (st_ok[g] && live[g]) ? off[g] : t0 * C;
+          xv[g] = *(const ulonglong2*)&xb[ld];
+          if constexpr (decltype(has_ab)::value)
+            av[g] = *(const ulonglong2*)&ab[ld];
         }
-        ob[t * C + co] = f2bf(v);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const float* srow = &St[(g * RPP + er) * SP + ec];
+          float s8[8];
+          *(float4*)&s8[0] = *(const float4*)&srow[0];
+          *(float4*)&s8[4] = *(const float4*)&srow[4];
+          bf16 x8[8], a8[8], o8[8];
+          *(ulonglong2*)x8 = xv[g];
+          if constexpr (decltype(has_ab)::value) *(ulonglong2*)a8 = av[g];
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            float v = s8[q] + bf2f(x8[q]);
+            if constexpr (decltype(has_ab)::value) v += bf2f(a8[q]);
+            v *= out_scale;
+            o8[q] = f2bf(live[g] ? v : 0.f);
+          }
+          if (st_ok[g]) *(ulonglong2*)&ob[off[g]] = *(ulonglong2*)o8;
+        }
+      };
+      if (ab) finish(std::true_type{});
+      else finish(std::false_type{});
+    }
+  } else {
+#pragma unroll
+    for (int mi = 0; mi < MT; ++mi) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const int m2 = wr * WM + mi * 16 + kl * 4 + rg;
+        const long t = t0 + m2;
+        if (m2 >= BM || t >= T) continue;
+        const bool live = t < lim;
+#pragma unroll
+        for (int nj = 0; nj < NT; ++nj) {
+          const int co = wc * WN + nj * 16 + il;
+          if (co >= C) continue;
+          float v = 0.f;
+          if (live) {
+            v = acc[mi][nj][rg] + b2r[nj] + bf2f(xb[t * C + co]);
+            if (ab) v += bf2f(ab[t * C + co]);
+            v *= out_scale;
+          }
+          ob[t * C + co] = f2bf(v);
+        }
       }
     }
   }
@@ -773,6 +907,26 @@ bool resblock_wlayout_sliced(long CP) {
   return sliced && CP >= 64;
 }
 
+// How the pair kernel's epilogue 2 reaches memory.
+// SONATA_RB_EPILOGUE=staged|direct is read on every call (like
+// SONATA_RB_GEOM); unset selects the default.
+//   staged: acc + b2 goes through wave-private f32 LDS tiles and the
+//           residual, accum and output move 16 bytes per lane
+//   direct: element-wise from the MFMA layout, 2 bytes per lane
+// Both run the same f32 operations in the same order: equal bit for bit
+// (tests/test_gpu_pair_epilogue.py).  Shapes staged cannot take (C not a
+// multiple of 8, unaligned tensors) run direct under either setting.
+#define RB_EPILOGUE_DEFAULT_STAGED true
+bool resblock_epilogue_staged() {
+  const char* e = getenv("SONATA_RB_EPILOGUE");
+  if (e && e[0]) {
+    TORCH_CHECK(strcmp(e, "staged") == 0 || strcmp(e, "direct") == 0,
+                "SONATA_RB_EPILOGUE must be staged or direct, got ", e);
+    return strcmp(e, "staged") == 0;
+  }
+  return RB_EPILOGUE_DEFAULT_STAGED;
+}
+
 // w_sliced says which weight layout the caller passes (it is never guessed):
 //   false: [k][CP][CP]         (tap, co, ci) - _conv_weight_mfma / perm_conv
 //   true:  [k][CP/32][CP][32]  (tap, K slice, co, ci in slice), CP >= 64 -
@@ -886,8 +1040,22 @@ static torch::Tensor resblock_pair_cl_impl(
   if (geom_env && strcmp(geom_env, "xtr128") == 0) geom64 = false;
   const long XTRh = (CP <= 32) ? 256 : (geom64 ? 64 : 128);
   const long BM = XTRh - (k - 1);
-#define LAUNCH_RB(BN, WGN, TC, XR, XTR)                                     \
-  hipLaunchKernelGGL((resblock_pair_cl_kernel<BN, WGN, TC, XR, XTR>),       \
+  // GEMM 2 reads k-1 Xt rows past the tile for output rows it discards;
+  // they must land inside Ws, which follows Xt in the kernel's LDS buffer.
+  {
+    const long tc = CP == 256 ? (geom64 ? 1 : 2)
+                              : (CP == 128 ? (geom64 ? 2 : 3) : 2);
+    TORCH_CHECK((k - 1) * (CP + 8) <= tc * CP * BKP,
+                "resblock_cl: kernel size ", k, " too large at CP ", CP);
+  }
+  // Epilogue 2 through LDS with 16-byte rows needs whole 8-channel groups
+  // and aligned rows; anything else takes the element-wise epilogue.
+  const auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  const bool staged = resblock_epilogue_staged() && C % 8 == 0 &&
+                      al16(x.data_ptr()) && al16(out.data_ptr()) &&
+                      al16(accum_p);
+#define LAUNCH_RB_(BN, WGN, TC, XR, XTR, ST)                                \
+  hipLaunchKernelGGL((resblock_pair_cl_kernel<BN, WGN, TC, XR, XTR, ST>),   \
                      dim3(ceil_div(T, BM), 1, B), dim3(512), 0, st,         \
                      (const bf16*)x.data_ptr(),                             \
                      (const bf16*)w1_perm.data_ptr(),                       \
@@ -896,6 +1064,11 @@ static torch::Tensor resblock_pair_cl_impl(
                      b2f.data_ptr<float>(), (bf16*)out.data_ptr(), accum_p, \
                      lens_p, (int)C, CP, T, (int)k, (int)dil,               \
                      (float)out_scale, wpitch, wkstep)
+#define LAUNCH_RB(BN, WGN, TC, XR, XTR)                                     \
+  do {                                                                      \
+    if (staged) LAUNCH_RB_(BN, WGN, TC, XR, XTR, true);                     \
+    else LAUNCH_RB_(BN, WGN, TC, XR, XTR, false);                           \
+  } while (0)
   // XR bucket = 128 + (k-1)*dil rounded up; TC=3 covers k=3 in one
   // chunk and k=7/11 in 3/4 chunks (fewer barrier pairs); C=256 keeps
   // TC=2 for LDS.
@@ -931,6 +1104,7 @@ static torch::Tensor resblock_pair_cl_impl(
 #undef RB_XR256
 #undef RB_XR64
 #undef LAUNCH_RB
+#undef LAUNCH_RB_
   return out;
 }
 
