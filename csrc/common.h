@@ -9,6 +9,7 @@
 #include <hip/hip_fp16.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #define WAVE 64
 
@@ -68,6 +69,93 @@ __device__ __forceinline__ void zero_tile_bf16(bf16* base, long nrows,
   }
   for (long r = tid / WAVE; r < nrows; r += nthreads / WAVE)
     zero_span_bf16(base + r * pitch + c0, ncols, tid % WAVE, WAVE);
+}
+
+// ------------------------------------------------------------------------
+// LDS staging of the channel-last MFMA conv kernels (conv1d_cl.hip,
+// resblock_cl.hip).  512 threads; a wave stages 16 rows of 32 channels per
+// pass of 128 rows, 16 bytes per lane: row sr_base0 + p*128 + sr_l, chunk
+// sr_c (the conflict-free lane map described in resblock_cl.hip).
+//
+// Both helpers issue every global load of their group first and only then
+// write LDS, with nothing conditional in between, so a group costs one
+// memory round trip instead of one per load.  Every condition therefore
+// sits outside the group or behind all of its loads: a test between one
+// load and its write makes the compiler wait for each load on its own.
+// ------------------------------------------------------------------------
+
+// Calls f(std::integral_constant<int, n>) for a runtime n in [1, N]: the
+// tap count of a staging window becomes a compile-time count chosen by one
+// uniform branch.
+template <int N, class F>
+__device__ __forceinline__ void with_count(int n, F&& f) {
+  if constexpr (N <= 1) {
+    f(std::integral_constant<int, 1>{});
+  } else {
+    if (n == N) f(std::integral_constant<int, N>{});
+    else with_count<N - 1>(n, f);
+  }
+}
+
+// One weight window: Ws[tc][row][sr_c..+8] = w[wbase + tc*tap_stride +
+// row*row_pitch + sr_c..+8] for NC taps and all BN rows.  NC is the exact
+// tap count of the window, so no tap beyond the kernel's last is read.
+// "Does this wave stage rows at all" (BN < 128) is tested once, around the
+// whole group.
+template <int NC, int BN, int PITCH>
+__device__ __forceinline__ void stage_w_window(
+    bf16 (*Ws)[BN][PITCH], const bf16* __restrict__ w, long wbase,
+    long tap_stride, long row_pitch, int sr_base0, int sr_l, int sr_c) {
+  static_assert(BN % 16 == 0 && (BN <= 128 || BN % 128 == 0),
+                "a wave's 16 rows of a pass are all inside BN or all outside");
+  constexpr int WPASS = (BN + 127) / 128;
+  if (sr_base0 < BN) {
+    // uniform base per (tap, pass) + one 32-bit lane offset for all of them
+    const int off = (sr_base0 + sr_l) * (int)row_pitch + sr_c;
+    ulonglong2 wv[NC][WPASS];
+#pragma unroll
+    for (int tc = 0; tc < NC; ++tc)
+#pragma unroll
+      for (int p = 0; p < WPASS; ++p) {
+        const bf16* wt = w + wbase + tc * tap_stride + p * 128 * row_pitch;
+        wv[tc][p] = *(const ulonglong2*)&wt[off];
+      }
+#pragma unroll
+    for (int tc = 0; tc < NC; ++tc)
+#pragma unroll
+      for (int p = 0; p < WPASS; ++p)
+        *(ulonglong2*)&Ws[tc][sr_base0 + p * 128 + sr_l][sr_c] = wv[tc][p];
+  }
+}
+
+// Interior x staging of one K slice: Xs[r][sr_c..+8] = pre(x0[r*C + sr_c..+8])
+// for r in [0, nrows), nrows <= XPASS*128, all rows and channels inside the
+// tensor.  A lane whose row is >= nrows loads row nrows-1 instead (a row the
+// group reads anyway) and writes nothing; pre is LeakyReLU(slope) where
+// do_pre (uniform), tested once around the group's arithmetic.  x0 is
+// uniform and nrows * C < 2^31 (nrows <= 384), so lane offsets are 32-bit.
+template <int XPASS, int PITCH>
+__device__ __forceinline__ void stage_x_interior(
+    bf16 (*Xs)[PITCH], const bf16* __restrict__ x0, long C, int nrows,
+    bool do_pre, float slope, int sr_base0, int sr_l, int sr_c) {
+  __attribute__((aligned(16))) bf16 v8[XPASS][8];
+#pragma unroll
+  for (int p = 0; p < XPASS; ++p) {
+    const int r = min(sr_base0 + p * 128 + sr_l, nrows - 1);
+    *(ulonglong2*)v8[p] = *(const ulonglong2*)&x0[r * (int)C + sr_c];
+  }
+  if (do_pre) {
+#pragma unroll
+    for (int p = 0; p < XPASS; ++p)
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        v8[p][q] = f2bf(lrelu_(bf2f(v8[p][q]), slope));
+  }
+#pragma unroll
+  for (int p = 0; p < XPASS; ++p) {
+    const int r = sr_base0 + p * 128 + sr_l;
+    if (r < nrows) *(ulonglong2*)&Xs[r][sr_c] = *(ulonglong2*)v8[p];
+  }
 }
 
 #define HIP_CHECK(expr)                                                     \

@@ -65,6 +65,11 @@ __global__ __launch_bounds__(512) void conv1d_cl_kernel(
 
   __shared__ bf16 Xs[ROWS][BKP];
   __shared__ bf16 Ws[TC][BN][BKP];
+  // Staging with all loads of a group issued before its LDS writes (see
+  // common.h).  The 128-column tile takes it; the narrow tiles keep one
+  // load per wait: batched they need 67-89 registers for 55/76 and lose a
+  // resident block each (KERNELS.md, pair/conv staging table).
+  constexpr bool BATCHED = BN >= 128;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -108,19 +113,25 @@ __global__ __launch_bounds__(512) void conv1d_cl_kernel(
     const bool c_interior = (c0 + BK) <= Cin;
     // ---- stage X rows: Xs[r][0..31] = pre(x[row0+r][c0..c0+31]) ------
     if (t_interior && c_interior) {
-      for (int base = sr_base0; base < rows_used; base += 128) {
-        const int r = base + sr_l;
-        if (r >= rows_used) continue;
-        const int ch = sr_c;
-        bf16 v8[8];
-        *(ulonglong2*)v8 =
-            *(const ulonglong2*)&xb[(row0 + r) * Cin + c0 + ch];
-        if (pre_slope >= 0.f) {
+      if constexpr (BATCHED) {
+        stage_x_interior<(ROWS + 127) / 128>(Xs, &xb[row0 * Cin + c0], Cin,
+                                             rows_used, pre_slope >= 0.f,
+                                             pre_slope, sr_base0, sr_l, sr_c);
+      } else {
+        for (int base = sr_base0; base < rows_used; base += 128) {
+          const int r = base + sr_l;
+          if (r >= rows_used) continue;
+          const int ch = sr_c;
+          bf16 v8[8];
+          *(ulonglong2*)v8 =
+              *(const ulonglong2*)&xb[(row0 + r) * Cin + c0 + ch];
+          if (pre_slope >= 0.f) {
 #pragma unroll
-          for (int q = 0; q < 8; ++q)
-            v8[q] = f2bf(lrelu_(bf2f(v8[q]), pre_slope));
+            for (int q = 0; q < 8; ++q)
+              v8[q] = f2bf(lrelu_(bf2f(v8[q]), pre_slope));
+          }
+          *(ulonglong2*)&Xs[r][ch] = *(ulonglong2*)v8;
         }
-        *(ulonglong2*)&Xs[r][ch] = *(ulonglong2*)v8;
       }
     } else {
       for (int base = sr_base0; base < rows_used; base += 128) {
@@ -155,13 +166,21 @@ __global__ __launch_bounds__(512) void conv1d_cl_kernel(
     for (int tap0 = 0; tap0 < ntaps; tap0 += TC) {
       const int ntc = min(TC, ntaps - tap0);
       // ---- stage W taps: Ws[tc][n][kk] = w[tap][n0+n][c0+kk] ---------
-      for (int tc = 0; tc < ntc; ++tc) {
-        const long wbase = ((long)(tap0 + tc) * CoutP + n0) * CinP + c0;
-        for (int base = sr_base0; base < BN; base += 128) {
-          const int n = base + sr_l;
-          const int ch = sr_c;
-          *(ulonglong2*)&Ws[tc][n][ch] =
-              *(const ulonglong2*)&w[wbase + (long)n * CinP + ch];
+      if constexpr (BATCHED) {
+        with_count<TC>(ntc, [&](auto nc) {
+          stage_w_window<decltype(nc)::value>(
+              Ws, w, ((long)tap0 * CoutP + n0) * CinP + c0,
+              (long)CoutP * CinP, CinP, sr_base0, sr_l, sr_c);
+        });
+      } else {
+        for (int tc = 0; tc < ntc; ++tc) {
+          const long wbase = ((long)(tap0 + tc) * CoutP + n0) * CinP + c0;
+          for (int base = sr_base0; base < BN; base += 128) {
+            const int n = base + sr_l;
+            const int ch = sr_c;
+            *(ulonglong2*)&Ws[tc][n][ch] =
+                *(const ulonglong2*)&w[wbase + (long)n * CinP + ch];
+          }
         }
       }
       __syncthreads();
@@ -492,20 +511,9 @@ __global__ __launch_bounds__(512) void convt1d_cl_kernel(
   for (int c0 = 0; c0 < CinP; c0 += BK) {
     const bool c_interior = (c0 + BK) <= Cin;
     if (t_interior && c_interior) {
-      for (int base = sr_base0; base < ROWS; base += 128) {
-        const int r = base + sr_l;
-        if (r >= ROWS) continue;
-        const int ch = sr_c;
-        bf16 v8[8];
-        *(ulonglong2*)v8 =
-            *(const ulonglong2*)&xb[(row0 + r) * Cin + c0 + ch];
-        if (pre_slope >= 0.f) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q)
-            v8[q] = f2bf(lrelu_(bf2f(v8[q]), pre_slope));
-        }
-        *(ulonglong2*)&Xs[r][ch] = *(ulonglong2*)v8;
-      }
+      stage_x_interior<(ROWS + 127) / 128>(Xs, &xb[row0 * Cin + c0], Cin,
+                                           ROWS, pre_slope >= 0.f,
+                                           pre_slope, sr_base0, sr_l, sr_c);
     } else {
       for (int base = sr_base0; base < ROWS; base += 128) {
         const int r = base + sr_l;
@@ -540,16 +548,9 @@ __global__ __launch_bounds__(512) void convt1d_cl_kernel(
     static_assert(NTAU % TAUC == 0, "tap chunking must divide evenly");
 #pragma unroll
     for (int cc = 0; cc < NTAU / TAUC; ++cc) {
-#pragma unroll
-      for (int tc = 0; tc < TAUC; ++tc) {
-        const long wbase = ((long)(cc * TAUC + tc) * CoutP + n0) * CinP + c0;
-        for (int base = sr_base0; base < BN; base += 128) {
-          const int n = base + sr_l;
-          const int ch = sr_c;
-          *(ulonglong2*)&Ws[tc][n][ch] =
-              *(const ulonglong2*)&w[wbase + (long)n * CinP + ch];
-        }
-      }
+      // (all loads of the window, then all LDS writes: see common.h)
+      stage_w_window<TAUC>(Ws, w, ((long)(cc * TAUC) * CoutP + n0) * CinP + c0,
+                           (long)CoutP * CinP, CinP, sr_base0, sr_l, sr_c);
       __syncthreads();
 
 #pragma unroll

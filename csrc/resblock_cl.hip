@@ -167,22 +167,26 @@ void resblock_pair_cl_kernel(
   const int sr_c = (lane & 3) * 8;     // staging chunk (bf16 offset)
   const int sr_base0 = wid * 16;       // wave's first row; stride 128
 
+  // One staging window of either GEMM: ntc taps x BN rows of the K slice
+  // at c0, in either weight layout.  The runtime tap count only picks the
+  // instantiation; inside it the window's loads are all issued before the
+  // first LDS write and nothing is tested in between (see common.h), and
+  // the count is exact, so no tap past k - 1 is addressed.
+  auto stage_w = [&](const bf16* __restrict__ w, int tap0, int c0, int ntc) {
+    const long wbase = ((long)tap0 * CP) * CP + (long)c0 * wkstep;
+    with_count<TC>(ntc, [&](auto nc) {
+      stage_w_window<decltype(nc)::value>(Ws, w, wbase, (long)CP * CP, wpitch,
+                                          sr_base0, sr_l, sr_c);
+    });
+  };
+
   for (int c0 = 0; c0 < CP; c0 += BK) {
     const bool c_interior = (c0 + BK) <= C;
     if (t_interior && c_interior) {
-      for (int base = sr_base0; base < xrows; base += 128) {
-        const int r = base + sr_l;
-        if (r < xrows) {
-          bf16 v8[8];
-          *(ulonglong2*)v8 =
-              *(const ulonglong2*)&xb[(row0 + r) * C + c0 + sr_c];
-#pragma unroll
-          for (int q = 0; q < 8; ++q)
-            v8[q] = f2bf(lrelu_(bf2f(v8[q]), 0.1f));
-          *(ulonglong2*)&Xs[r][sr_c] = *(ulonglong2*)v8;
-        }
-      }
+      stage_x_interior<(XR + 127) / 128>(Xs, &xb[row0 * C + c0], C, xrows,
+                                         true, 0.1f, sr_base0, sr_l, sr_c);
     } else {
+      // edge tiles and C < CP only: element loads, each waited for alone
       for (int base = sr_base0; base < xrows; base += 128) {
         const int r = base + sr_l;
         if (r >= xrows) continue;
@@ -199,15 +203,7 @@ void resblock_pair_cl_kernel(
     }
     for (int tap0 = 0; tap0 < k; tap0 += TC) {
       const int ntc = min(TC, k - tap0);
-      for (int tc = 0; tc < ntc; ++tc) {
-        const long wbase =
-            ((long)(tap0 + tc) * CP) * CP + (long)c0 * wkstep;
-        for (int base = sr_base0; base < BN; base += 128) {
-          const int n = base + sr_l;
-          *(ulonglong2*)&Ws[tc][n][sr_c] =
-              *(const ulonglong2*)&w1[wbase + (long)n * wpitch + sr_c];
-        }
-      }
+      stage_w(w1, tap0, c0, ntc);
       __syncthreads();
       for (int tc = 0; tc < ntc; ++tc) {
         const int toff = (tap0 + tc) * dil;
@@ -264,15 +260,7 @@ void resblock_pair_cl_kernel(
   for (int c0 = 0; c0 < CP; c0 += BK) {
     for (int tap0 = 0; tap0 < k; tap0 += TC) {
       const int ntc = min(TC, k - tap0);
-      for (int tc = 0; tc < ntc; ++tc) {
-        const long wbase =
-            ((long)(tap0 + tc) * CP) * CP + (long)c0 * wkstep;
-        for (int base = sr_base0; base < BN; base += 128) {
-          const int n = base + sr_l;
-          *(ulonglong2*)&Ws[tc][n][sr_c] =
-              *(const ulonglong2*)&w2[wbase + (long)n * wpitch + sr_c];
-        }
-      }
+      stage_w(w2, tap0, c0, ntc);
       __syncthreads();
       for (int tc = 0; tc < ntc; ++tc) {
         const int toff = tap0 + tc;  // d=1
