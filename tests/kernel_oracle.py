@@ -554,6 +554,21 @@ def assert_within(got: torch.Tensor, oracle: Oracle, *, tile: int = 0,
             f"{float(bound[idx]):.3e}")
 
 
+def assert_plus_zero(got: torch.Tensor, lens: torch.Tensor, what: str = "",
+                     time_dim: int = 1) -> None:
+    """Rows t >= lens[b] of a bf16 tensor hold the bit pattern of +0
+    (0x0000), not -0: the kernels store zeros there, they do not multiply
+    by a mask."""
+    assert got.dtype == torch.bfloat16, f"{what}: {got.dtype}"
+    g = got.detach().cpu().movedim(time_dim, 1).contiguous()
+    bits = g.view(torch.int16).reshape(g.shape[0], g.shape[1], -1)
+    masked = row_mask(lens, g.shape[0], g.shape[1])
+    leak = (bits != 0) & masked.unsqueeze(-1)
+    assert not leak.any(), (
+        f"{what}: {int(leak.sum())} masked elements are not +0; first at "
+        f"(b, t, c) = {tuple(int(i) for i in leak.nonzero()[0])}")
+
+
 def rounding_free(shape, gen, scale=1.0, dtype=torch.bfloat16):
     """Random bf16-representable tensor (so the reference input is
     unambiguous)."""

@@ -59,14 +59,7 @@ def _nan_past(t, lens, gap=NAN_GAP):
     return t.masked_fill(far, float("nan"))
 
 
-def _assert_plus_zero(got, lens, what):
-    """Rows t >= lens[b] hold the bit pattern of +0 (0x0000), not -0."""
-    bits = got.detach().cpu().contiguous().view(torch.int16)
-    masked = ko.row_mask(lens, got.shape[0], got.shape[1])
-    leak = (bits != 0) & masked.unsqueeze(-1)
-    assert not leak.any(), (
-        f"{what}: {int(leak.sum())} masked elements are not +0; first at "
-        f"{tuple(int(i) for i in leak.nonzero()[0])}")
+_assert_plus_zero = ko.assert_plus_zero
 
 
 def _pair_bm(C, k):

@@ -53,12 +53,7 @@ def _bits(t):
     return t.detach().cpu().contiguous().view(torch.int16)
 
 
-def _assert_plus_zero(got, lens, what):
-    masked = ko.row_mask(lens, got.shape[0], got.shape[1])
-    leak = (_bits(got) != 0) & masked.unsqueeze(-1)
-    assert not leak.any(), (
-        f"{what}: {int(leak.sum())} masked elements are not +0; first at "
-        f"{tuple(int(i) for i in leak.nonzero()[0])}")
+_assert_plus_zero = ko.assert_plus_zero
 
 
 def _xtr(C, geom):
